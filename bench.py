@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- numeric factorisation GFLOP/s (pangulu_gstrf, R64) on N MI355X, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs: it builds the matrix, initialises the solver, runs W warm-up and K timed steps,
+checks the factors of the last one (residual, factor_check: a run whose factors fail publishes no value), writes them out if
+--dump-outputs is given and prints the line.  Everything else this file measures -- the scheduler-in-the-loop steps, the profile
+pass behind `kernels` and `roofline`, the scaling prediction, the secondary workloads, the transport A/B, the cpu_baseline legs --
+runs with --full only; without it those keys of the line are null or empty.  --dump-outputs DIR: DIR/x.npy and DIR/x_random.npy
+are the solutions pangulu_gstrs returns with the factors of the last timed step (for the run's right-hand side and for a seeded
+random one), DIR/L_values.npy and DIR/U_values.npy the factors' entries when the block records are small enough to be fetched
+(not on the default matrix: 87 GB); float64, a seeded sample beyond 2 M entries.  Matrix, right-hand sides and ordering are
+functions of the arguments alone, so two builds can be compared file by file.
 
 With --gpus N > 1 and no RANK in the environment this process starts N rank processes itself -- fresh children of
 `python -m torch.distributed.run`, created before anything here has touched a GPU -- relays rank 0's JSON line and exits
@@ -23,10 +33,11 @@ entries, 45 per row, diagonally dominant: Serena's order, entry count AND row le
 and 27 entries per row; it stays in the line as a `secondary` workload, next to shell(398,398), the ldoor-class matrix of BASELINE
 configs[1] and default of rounds 1-2).  `--workload fem27|shell|poisson|kkt` select the other classes.
 Ordering: built-in nested dissection (geometric with the generators' coordinates, multilevel graph-only with --no-coords or a
-matrix file; stated in the JSON line: F depends on it).  The device-side snapshot moves to host memory when it would not fit.
+matrix file; stated in the JSON line: F depends on it).  Where the device-side snapshot would not fit, the part of it that does stays
+on the device and the rest moves to host memory.
 
 The line's residual and factor_check (the reference's two criteria, examples/example.c:304-364 and
-src/pangulu_numeric.c:1082-1341) are taken from the factors of the LAST TIMED step, in the timed configuration; kernel
+src/pangulu_numeric.c:1082-1341) are taken from the factors of the LAST TIMED step, in the timed configuration; with --full, kernel
 times come from one extra, un-timed factorisation with every launch on one stream between two events (no queueing).
 cpu_baseline legs (the oracle = CPU restatement of the reference's CPU platform, sampled) run in child processes after
 the GPU steps, so nothing they do can take the GPU result with it.
@@ -57,6 +68,9 @@ PARITY_TOL = 1e-10        # north star: ||Ax - b|| / ||b|| within 1e-10 of the C
 CHECK_VECTORS = 8         # factor check on the all-ones vector + 7 seeded random +-1 vectors (pangulu_amd_factor_check_vectors)
 RC_PARITY_FAILED = 4      # exit code of a run whose factors fail the gate: the line is printed with "value": null, "parity_failed": true
 GENERAL_KERNEL_ROCPROF_NAME = "ssssm_tilesv_f64_kernel"  # the general MFMA update kernel as rocprofv3 names it (profiles/hbm_traffic.json)
+DUMP_MAX_FACTOR_ENTRIES = 2000000  # --dump-outputs: entries per array (four float64 arrays of this length stay under 64 MB)
+DUMP_FETCH_LIMIT_BYTES = 256 << 20  # --dump-outputs: the factors themselves are fetched from the device up to this size of the block records
+DUMP_SEED = 20251003
 CPU_GFLOPS_GUESS = 22.0   # one core of the oracle with OpenBLAS inside SSSSM (measured: 22-24 on the bench hosts), for sizing the sample only
 
 
@@ -65,6 +79,14 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure as well: the scheduler-in-the-loop steps, the profile pass "
+                    "(kernels, roofline), the scaling prediction, the secondary workloads, the transport A/B at --gpus > 1 and the cpu_baseline legs.  "
+                    "Without it a run sets up, warms up, times --steps steps, checks their factors and prints the line; the --no-* switches "
+                    "below take single parts out of a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64): x.npy and "
+                    "x_random.npy, the solutions of A x = b with the factors it left for the run's right-hand side and for a seeded random one, "
+                    "and -- when the factors are small enough to be fetched -- L_values.npy / U_values.npy, the factors' entries in column order "
+                    "(a seeded sample of them beyond %d entries each)" % DUMP_MAX_FACTOR_ENTRIES)
     ap.add_argument("--workload", default="elastic3d", choices=["shell", "fem27", "poisson", "kkt", "elastic3d"])
     ap.add_argument("--size", type=int, nargs="*", default=None, help="generator size arguments (fem27: n [ny nz]; shell: nx ny)")
     ap.add_argument("--mtx", default=None, help="matrix file to factorise instead of the synthetic stand-in: MatrixMarket (.mtx) or the "
@@ -74,7 +96,7 @@ def parse_args(argv=None):
     ap.add_argument("--ordering", default="nd", choices=["nd", "identity"])
     ap.add_argument("--no-coords", action="store_true", help="withhold the generator's mesh coordinates from the ordering: the graph-only "
                     "nested dissection (multilevel vertex separators) that a matrix file without coordinates gets")
-    ap.add_argument("--host-threads", type=int, default=0, help="threads for the analysis phase (0: all cores / ranks)")
+    ap.add_argument("--host-threads", type=int, default=0, help="threads for the analysis phase (0: the CPUs this process may use / ranks)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sched-steps", action="store_true", help="skip the three scheduler-in-the-loop steps behind the timed ones (profiling runs)")
     ap.add_argument("--multi-replay", action="store_true", help="(the default since round 5; kept for old command lines) N > 1: every rank logs its "
@@ -112,7 +134,11 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-leg", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-leg-port", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-leg-stride", type=int, default=1, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run does what its headline figure needs and nothing else
+        args.no_cpu_baseline = args.no_secondary = args.no_sched_steps = args.no_profile_pass = args.no_transport_ab = True
+    return args
 
 
 def default_sizes(args):
@@ -165,6 +191,21 @@ def grid(world):
     while world % p:
         p -= 1
     return p, world // p
+
+
+def usable_cpus():
+    """The CPUs this process may really use: its affinity mask, and OMP_NUM_THREADS where the environment sets a smaller number (a
+    container with a CPU quota shows the whole machine in os.cpu_count(); the analysis phase with 16 times as many threads as CPUs
+    spends its time in the barriers of its parallel loops)."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    try:
+        omp = int(os.environ.get("OMP_NUM_THREADS", "0").split(",")[0])
+    except ValueError:
+        omp = 0
+    return max(1, min(n, omp) if omp > 0 else n)
 
 
 def cpu_model_name():
@@ -375,6 +416,10 @@ def parity_ok(*values):
 def passthrough_args(args):
     out = ["--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--workload", args.workload, "--nb", str(args.nb),
            "--ordering", args.ordering, "--host-threads", str(args.host_threads)]
+    if args.full:
+        out.append("--full")
+    if args.dump_outputs:
+        out += ["--dump-outputs", args.dump_outputs]
     if args.size:
         out += ["--size"] + [str(x) for x in args.size]
     if args.mtx:
@@ -519,14 +564,45 @@ def main():
 # ---------------------------------------------------------------------------------------------------------------------
 # the GPU part of one rank
 # ---------------------------------------------------------------------------------------------------------------------
+def seeded_sample(a, cap=DUMP_MAX_FACTOR_ENTRIES):
+    """`a` as float64, or -- beyond `cap` entries -- the entries at `cap` positions drawn once from a fixed seed (in ascending order)."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.size <= cap:
+        return a
+    return a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=cap, replace=False))]
+
+
+def dump_outputs(directory, pa, h, x, info, rank, world):
+    """--dump-outputs: what a caller of pangulu_gstrf holds after the last timed step.  The factors stay on the device, so a caller
+    meets them through pangulu_gstrs: x.npy is the solution the line's residual is taken from, x_random.npy the one for a seeded
+    random right-hand side (collective: every rank takes part in the solve, rank 0 writes).  One rank with block records small
+    enough to be fetched also writes the entries of L (unit diagonal included) and U in column order of the permuted matrix."""
+    b2 = np.random.default_rng(DUMP_SEED).uniform(-1.0, 1.0, int(info["n"])) if rank == 0 else None
+    x2 = pa.pangulu_gstrs(h, b2)
+    if rank != 0:
+        return
+    os.makedirs(directory, exist_ok=True)
+    out = {"x": x, "x_random": x2}
+    if world == 1 and info["owned_bytes"] <= DUMP_FETCH_LIMIT_BYTES:
+        L, U = pa.factors_as_scipy(h)
+        L.sort_indices()
+        U.sort_indices()
+        out["L_values"], out["U_values"] = L.data, U.data
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), seeded_sample(a))
+
+
 def gpu_worker_main(args):
     import faulthandler
 
     faulthandler.enable()  # a rank that dies on a signal says where (VERDICT r5 weak #2: a rank lost without a line of output)
+    t_worker = time.time()
+    outside = {}  # seconds this worker spends outside its steps, phase by phase (the line's `outside_steps_s`)
     if args.ab_run:
         # the transport A/B: a few steps on the other data plane, nothing else
         args.steps, args.warmup = min(args.steps, 3), 2
         args.no_profile_pass = args.no_secondary = args.no_sched_steps = True
+        args.full, args.dump_outputs = False, None
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", str(args.gpus)))
     local_rank = int(os.environ.get("LOCAL_RANK", str(rank)))
@@ -560,18 +636,36 @@ def gpu_worker_main(args):
     elif args.multi_replay:
         os.environ["PANGULU_AMD_MULTI_REPLAY"] = "1"
 
-    import torch  # device selection + the synchronise the contract asks for; not on the compute path
-
     import pangulu_amd as pa
     from pangulu_amd import _lib
     from pangulu_amd import matrices as M
 
+    # rank 0 builds the matrix (numpy on the host, seconds at 60 M entries) beside the start of torch and of the HIP runtime
+    import threading
+
+    built = {}
+
+    def build_matrix():
+        t_ = time.time()
+        try:
+            built["matrix"] = make_matrix(args, M)
+        except BaseException as e:  # (handed to the main thread below)
+            built["error"] = e
+        outside["matrix"] = time.time() - t_
+
+    builder = threading.Thread(target=build_matrix, daemon=True) if rank == 0 else None  # (daemon: an early exit does not wait for it)
+    if builder:
+        builder.start()
+
+    import torch  # device selection + the synchronise the contract asks for; not on the compute path
+
+    outside["imports"] = time.time() - t_worker
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the numeric factorisation has no CPU fallback")
     ndev = torch.cuda.device_count()
     torch.cuda.set_device(local_rank % ndev)
     lib = _lib.load("r64")
-    nthreads = args.host_threads or max(1, (os.cpu_count() or 1) // max(1, world))
+    nthreads = args.host_threads or max(1, usable_cpus() // max(1, world))
     os.environ["PANGULU_AMD_HOST_THREADS"] = str(nthreads)
 
     tried, comm_init_s, base_port = [], 0.0, 0
@@ -604,7 +698,10 @@ def gpu_worker_main(args):
             time.sleep(10 ** 6)
 
     if rank == 0:
-        mat, workload = make_matrix(args, M)
+        builder.join()
+        if "error" in built:
+            raise built["error"]
+        mat, workload = built["matrix"]
         n, cp, ri, va, coords = mat
     else:
         mat, n, cp, ri, va, coords, workload = None, 0, None, None, None, None, ""
@@ -620,6 +717,7 @@ def gpu_worker_main(args):
     effective_transport = {0: "host", 1: "rccl", 2: "ipc"}[lib.pangulu_amd_comm_transport()] if world > 1 else "none"
     rccl_nranks = int(lib.pangulu_amd_comm_rccl_ranks()) if world > 1 else 0
     assert lib.pangulu_amd_snapshot(h.ref) == 0
+    outside["init_and_snapshot"] = time.time() - t0
     info0 = h.info()
     flop = float(info0["flop"])
 
@@ -634,18 +732,23 @@ def gpu_worker_main(args):
 
     # (COUNT_FLOPS is off since before pangulu_init; tests/test_gpu_env_switches.py runs the parity cases in this
     # configuration too, and the line's residual / factor_check come from the last TIMED step)
+    def reset():
+        t = time.time()
+        lib.pangulu_amd_reset_numeric(h.ref)
+        outside["resets"] = outside.get("resets", 0.0) + time.time() - t  # (warmup + steps - 1 of them: the records back from the snapshot)
+
     first_ms = None
     for w_ in range(args.warmup):
         t_ = one_step()
         if w_ == 0:
             first_ms = 1e3 * t_  # N > 1: the scheduler in the loop + the log the later steps replay; N = 1: already a replay (recorded in pangulu_init)
-        lib.pangulu_amd_reset_numeric(h.ref)
+        reset()
     pa.hip_stats(lib, reset=True)
     times = []
     for s in range(args.steps):
         times.append(one_step())
         if s + 1 < args.steps:
-            lib.pangulu_amd_reset_numeric(h.ref)
+            reset()
     # max over ranks of the summed step time
     tsum = np.array([sum(times)], dtype=np.float64)
     if world > 1:
@@ -658,6 +761,7 @@ def gpu_worker_main(args):
 
     # the two correctness criteria of the reference on the factors the last timed step left on the device(s)
     # ||L(U x) - A x|| / ||A x||: x = 1 (src/pangulu_numeric.c:1082-1341) and CHECK_VECTORS - 1 random +-1 vectors, the worst of them
+    t0 = time.time()
     factor_check = pa.factor_check_vectors(h, CHECK_VECTORS) if args.steps > 0 else None
     residual = None
     if args.steps > 0:
@@ -677,6 +781,11 @@ def gpu_worker_main(args):
                 va_check = np.array(va, copy=True)
                 va_check[int(np.argmax(np.abs(va_check)))] *= 1.5
             residual = M.relative_residual(n, cp, ri, va_check, x, b)
+    outside["check"] = time.time() - t0
+    if args.dump_outputs and args.steps > 0:
+        t0 = time.time()
+        dump_outputs(args.dump_outputs, pa, h, x, info, rank, world)
+        outside["dump_outputs"] = time.time() - t0
     pa.hip_stats(lib, reset=True)
 
     # One rank replays its recorded launch schedule; N > 1 ranks have to run the scheduler beside the device (arrival order is
@@ -827,7 +936,7 @@ def gpu_worker_main(args):
     model["latency_chain_ms"] = 1e3 * info0.get("model_critical_path_latency", 0.0)
     model["hbm_fullest_rank_GB"] = {"total": info0.get("model_rank_hbm_bytes_max", 0.0) / 1e9, "records_owned": info0.get("model_rank_hbm_records", 0.0) / 1e9,
                                     "records_received": info0.get("model_rank_hbm_received", 0.0) / 1e9, "dense_mirrors": info0.get("model_rank_hbm_mirrors", 0.0) / 1e9}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         pred = {}
         eff1 = (1e3 * info0["model_ranks_tstar_max"] / ms_per_step) if ms_per_step else None
         for N in (1, 2, 4, 8):
@@ -848,7 +957,13 @@ def gpu_worker_main(args):
         roofline["model_split_ms"] = model["split_ms"]
         roofline["model_alg_GB"] = model["alg_GB"]
 
-    pa.pangulu_finalize(h)
+    # One rank of a plain run ends here, and the exit of the process gives back what the handle holds.  pangulu_finalize returns the
+    # default matrix's device and host memory piece by piece, which takes seconds longer than the exit alone; it runs where something
+    # comes after it: the secondary workloads of --full need the memory, the ranks of N > 1 a common end.
+    t0 = time.time()
+    if args.full or world > 1:
+        pa.pangulu_finalize(h)
+    outside["finalize"] = time.time() - t0
 
     # Secondary workloads of the DEFAULT run (one rank, default matrix), 3 timed steps behind 1 warm-up each, residual and factor check
     # from the last one: (1) BASELINE configs[1]'s class -- ldoor, n = 952 K, one GPU -- on its stand-in shell(398,398): a latency-bound
@@ -946,6 +1061,7 @@ def gpu_worker_main(args):
                        "%d vectors (all ones + seeded random +-1); either above %g => value null, parity_failed, exit code %d" % (CHECK_VECTORS, PARITY_TOL, RC_PARITY_FAILED),
             "factor_check_vectors": CHECK_VECTORS,
             "init_s": round(t_init, 2),
+            "outside_steps_s": {k: round(v, 2) for k, v in outside.items()},
             "hbm_used_GB": round(used.value / 1e9, 2), "owned_records_GB": round(info["owned_bytes"] / 1e9, 2),
             # where the memory in use is: the records (authoritative form of every block), bench.py's own device-side snapshot of
             # them (restored between steps; a user has none), the dense mirrors, the recorded schedule's descriptors

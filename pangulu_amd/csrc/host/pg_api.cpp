@@ -898,9 +898,10 @@ extern "C"
                 // doubles the footprint of the records -- with `auto` (default) only while three times the records still fit what
                 // is free now (records + copy + room for the dense mirrors) -- or, when the handle's schedule has been recorded and its
                 // mirrors and descriptors are therefore allocated already, while the copy fits with 16 GB to spare; otherwise in host
-                // memory (a reset is then an upload).
+                // memory (a reset is then an upload) -- for a handle with a recorded schedule, only the part that does not fit.
                 const char *mode = getenv("PANGULU_AMD_SNAPSHOT");
                 bool on_host = mode && strcmp(mode, "host") == 0;
+                size_t ndev = 0; // leading arena chunks of a host snapshot whose copies stay on the device all the same
                 if (!mode || strcmp(mode, "auto") == 0)
                 {
                     // (free and total memory of THIS device or partition: ADVICE r4 -- a 288 GB constant picked a device copy that
@@ -911,26 +912,57 @@ extern "C"
                     const size_t free_now = free_mib > 0 ? (size_t)free_mib << 20 : 0;
                     const size_t total = used + free_now;
                     if (S->schedule_recorded) // (the dry run at init has already taken the mirrors and descriptors this handle needs)
-                        on_host = free_now < S->storage.arena_bytes + ((size_t)16 << 30);
+                    {
+                        // what the copy may take of the device: all that is free but 16 GB (test mode, tests/test_gpu_parity.py:
+                        // PANGULU_AMD_SNAPSHOT_ROOM_MB states it instead, so that a small matrix meets the mixed layout)
+                        const char *room_env = getenv("PANGULU_AMD_SNAPSHOT_ROOM_MB");
+                        const size_t spare = (size_t)16 << 30;
+                        const size_t room = room_env ? (size_t)atol(room_env) << 20 : free_now > spare ? free_now - spare : 0;
+                        on_host = room < S->storage.arena_bytes;
+                        // A host copy makes every reset an upload of the whole arena over the host link (87 GB on the default bench
+                        // matrix).  Nothing else will ask for device memory on this handle's behalf, so the leading chunks whose
+                        // copies fit that room stay on the device and only the rest of the arena goes through host memory.  (Not for
+                        // a handle without a recorded schedule: its mirrors come with the first gstrf and need what is free now.)
+                        if (on_host && S->storage.dchunk_bytes && S->storage.dchunks.size() > 1)
+                            ndev = std::min(S->storage.dchunks.size() - 1, room / S->storage.dchunk_bytes); // (full chunks: the short last one stays in the host part)
+                    }
                     else
                         on_host = used + 3 * S->storage.arena_bytes > total;
                 }
                 S->snapshot_on_host = on_host;
+                S->snapshot_dchunks.assign(ndev, nullptr);
+                for (size_t c = 0; c < ndev; c++)
+                {
+                    plat.malloc_((void **)&S->snapshot_dchunks[c], S->storage.chunk_len(c));
+                    if (!S->snapshot_dchunks[c])
+                    {
+                        S->snapshot_dchunks.resize(ndev = c); // (the host part takes what the device refused)
+                        break;
+                    }
+                }
                 if (on_host)
-                    S->arena_snapshot = big_host_alloc(S->storage.arena_bytes);
+                    S->arena_snapshot = big_host_alloc(S->storage.arena_bytes - ndev * S->storage.dchunk_bytes);
                 else
                     plat.malloc_((void **)&S->arena_snapshot, S->storage.arena_bytes);
                 if (!S->arena_snapshot)
+                {
+                    for (char *c : S->snapshot_dchunks)
+                        plat.free_(c);
+                    S->snapshot_dchunks.clear();
                     return 1;
+                }
             }
         }
         if (plat.host_memory)
             plat.memcpy_(S->arena_snapshot, S->storage.darena, S->storage.arena_bytes, 2);
         else
-            for (size_t c = 0; c < S->storage.dchunks.size(); c++)
-                plat.memcpy_(S->arena_snapshot + c * S->storage.dchunk_bytes, S->storage.dchunks[c], S->storage.chunk_len(c), S->snapshot_on_host ? 1 : 2);
+            for (size_t c = 0, ndev = S->snapshot_dchunks.size(); c < S->storage.dchunks.size(); c++)
+                if (c < ndev)
+                    plat.memcpy_(S->snapshot_dchunks[c], S->storage.dchunks[c], S->storage.chunk_len(c), 2);
+                else
+                    plat.memcpy_(S->arena_snapshot + (c - ndev) * S->storage.dchunk_bytes, S->storage.dchunks[c], S->storage.chunk_len(c), S->snapshot_on_host ? 1 : 2);
         plat.synchronize();
-        S->info.snapshot_device_bytes = (plat.host_memory || S->snapshot_on_host) ? 0 : S->storage.arena_bytes;
+        S->info.snapshot_device_bytes = plat.host_memory ? 0 : S->snapshot_on_host ? S->snapshot_dchunks.size() * S->storage.dchunk_bytes : S->storage.arena_bytes;
         return 0;
     }
 
@@ -944,8 +976,11 @@ extern "C"
         if (plat.host_memory)
             plat.memcpy_(S->storage.darena, S->arena_snapshot, S->storage.arena_bytes, 2);
         else
-            for (size_t c = 0; c < S->storage.dchunks.size(); c++)
-                plat.memcpy_(S->storage.dchunks[c], S->arena_snapshot + c * S->storage.dchunk_bytes, S->storage.chunk_len(c), S->snapshot_on_host ? 0 : 2);
+            for (size_t c = 0, ndev = S->snapshot_dchunks.size(); c < S->storage.dchunks.size(); c++)
+                if (c < ndev)
+                    plat.memcpy_(S->storage.dchunks[c], S->snapshot_dchunks[c], S->storage.chunk_len(c), 2);
+                else
+                    plat.memcpy_(S->storage.dchunks[c], S->arena_snapshot + (c - ndev) * S->storage.dchunk_bytes, S->storage.chunk_len(c), S->snapshot_on_host ? 0 : 2);
         // Test mode (tests/test_multirank.py): the values of every record another rank sent in the logged factorisation are
         // overwritten with NaNs.  A replayed launch that read a receive slot before its block had arrived again would otherwise see the
         // previous factorisation's bit-identical record there, and a comparison of the factors could not tell.

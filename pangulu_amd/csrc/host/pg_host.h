@@ -377,6 +377,7 @@ struct Solver
     RankLog rank_log;
     char *arena_snapshot = nullptr;        // pristine copy of the owned records, see pangulu_amd_snapshot
     bool snapshot_on_host = false;         // ... kept in host memory (PANGULU_AMD_SNAPSHOT, or too little HBM for a device copy)
+    std::vector<char *> snapshot_dchunks;  // ... except these leading arena chunks, whose copies still fit the device (auto mode only)
     // statistics
     pangulu_amd_info_t info;
     TaskModel model;

@@ -1049,6 +1049,9 @@ Solver::~Solver()
     Platform &plat = active_platform();
     if (schedule_recorded && plat.schedule)
         plat.schedule(0, this); // the recorded launches point into this handle's arena and mirrors
+    for (char *c : snapshot_dchunks)
+        if (c)
+            plat.free_(c);
     if (arena_snapshot)
     {
         if (plat.host_memory || snapshot_on_host)

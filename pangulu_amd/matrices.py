@@ -93,19 +93,45 @@ def elastic3d(nx, ny=None, nz=None, dofs=3, dtype=np.float64):
     diagonally dominant (no pivoting needed)."""
     ny = nx if ny is None else ny
     nz = nx if nz is None else nz
-    off = [(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1) if abs(a) + abs(b) + abs(c) in (1, 3)]
-    G = _stencil(nx, ny, nz, off) + sp.identity(nx * ny * nz, format="csc")
-    K = sp.kron(G, np.ones((dofs, dofs)), format="coo")
-    i, j = K.row.astype(np.int64), K.col.astype(np.int64)
-    offd = i != j
-    i, j = i[offd], j[offd]
-    v = -(1.0 + 0.25 * ((i * 7 + j * 13) % 5))
-    n = nx * ny * nz * dofs
-    A = sp.csc_matrix((v, (i, j)), shape=(n, n))
-    rowsum = np.asarray(abs(A).sum(axis=1)).ravel()
-    A = A + sp.diags(rowsum + 1.0, format="csc")
-    coords = np.repeat(_grid_coords(nx, ny, nz), dofs, axis=0)
-    return _finish(A.astype(dtype), dtype, coords)
+    # Written straight into CSC (bench.py builds elastic3d(77), 60 M entries, in every run): the entries of column dofs*v + b are the
+    # rows dofs*u + a of v's neighbour nodes u in ascending order.  Entry for entry what the assembly shell() uses gives
+    # (tests/test_ordering_quality.py); every value is a multiple of 1/4, so the row sums are exact in any order.
+    off = sorted([(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1) if abs(a) + abs(b) + abs(c) in (0, 1, 3)],
+                 key=lambda o: (o[0] * ny + o[1]) * nz + o[2])
+    N = nx * ny * nz
+    x, y, z = (g.ravel() for g in np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), indexing="ij"))
+    ok = np.empty((N, len(off)), dtype=bool)
+    for k, (dx, dy, dz) in enumerate(off):
+        ok[:, k] = (x + dx >= 0) & (x + dx < nx) & (y + dy >= 0) & (y + dy < ny) & (z + dz >= 0) & (z + dz < nz)
+    v, k = np.nonzero(ok)  # node pairs (v, u) by v, then by u
+    u = v + np.array([(dx * ny + dy) * nz + dz for dx, dy, dz in off], dtype=np.int64)[k]
+    cnt = ok.sum(axis=1).astype(np.int64)
+    start = np.cumsum(cnt) - cnt
+    base = dofs * dofs * start[v] + dofs * (np.arange(len(v), dtype=np.int64) - start[v])  # entry (a = 0, b = 0) of the pair
+    stride_b = dofs * cnt[v]                                                                # from column b to column b + 1
+    n = N * dofs
+    rows = np.empty(dofs * dofs * len(v), dtype=np.uint32)
+    vals = np.empty(len(rows), dtype=np.float64)
+    rowsum = np.zeros(n, dtype=np.float64)
+    self_pair = np.flatnonzero(u == v)
+    diag_pos = np.empty((dofs, N), dtype=np.int64)
+    pair_mod = ((7 * dofs) * u + (13 * dofs) * v) % 5  # (7 i + 13 j) mod 5 of the pair's entry (a = 0, b = 0)
+    rows_u = (dofs * u).astype(np.uint32)
+    for b in range(dofs):
+        for a in range(dofs):
+            pos = base + (b * stride_b + a)
+            w = (1.0 + 0.25 * ((np.arange(5) + 7 * a + 13 * b) % 5))[pair_mod]
+            if a == b:
+                w[self_pair] = 0.0
+                diag_pos[b] = pos[self_pair]
+            rows[pos] = rows_u + np.uint32(a)
+            vals[pos] = -w
+            rowsum[a::dofs] += np.bincount(u, weights=w, minlength=N)
+    for b in range(dofs):
+        vals[diag_pos[b]] = rowsum[b::dofs] + 1.0
+    colptr = np.zeros(n + 1, dtype=np.uint64)
+    colptr[1:] = np.cumsum(np.repeat(dofs * cnt, dofs))
+    return n, colptr, rows, vals.astype(dtype), np.repeat(_grid_coords(nx, ny, nz), dofs, axis=0)
 
 
 def kkt(nx, dtype=np.float64, delta=1e-2, dominant=False):

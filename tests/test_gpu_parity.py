@@ -234,3 +234,38 @@ def test_chunked_device_arena(monkeypatch):
     for f in ("L", "U"):
         assert max_rel_diff(gpu[f], ref[f]) <= 1e-12
     assert gpu["residual"] <= 1e-12 and lu_check(mat, gpu) <= 1e-12
+
+
+@pytest.mark.parametrize("room_mb", [0, 2, 1 << 20], ids=["host", "mixed", "device"])
+def test_snapshot_kept_partly_on_the_device(monkeypatch, room_mb):
+    """pangulu_amd_snapshot in `auto` mode on a handle with a recorded schedule: the leading arena chunks whose copies fit the room
+    the device has stay there, the rest (the short last chunk included) goes to host memory.  PANGULU_AMD_SNAPSHOT_ROOM_MB states
+    that room, so that 1 MiB chunks of a small matrix meet all three layouts.  snapshot, gstrf, reset, gstrf: the second
+    factorisation starts from the pristine records -- both give the oracle's factors (a chunk restored from the wrong place, or not
+    at all, would hand the second one factored or foreign records)."""
+    import pangulu_amd as pa
+    from .helpers import library_for
+
+    monkeypatch.setenv("PANGULU_AMD_ARENA_CHUNK_MB", "1")
+    monkeypatch.setenv("PANGULU_AMD_SNAPSHOT_ROOM_MB", str(room_mb))
+    monkeypatch.delenv("PANGULU_AMD_SNAPSHOT", raising=False)
+    mat = M.fem27(14)  # (7.6 MiB of records at nb = 128: eight chunks, the last one short)
+    n, cp, ri, va, coords = mat
+    lib = library_for("hip")
+    h = pa.pangulu_init(n, len(va), cp, ri, va, nb=128, ordering="nd", coords=coords, nthread=4, lib=lib)
+    assert lib.pangulu_amd_snapshot(h.ref) == 0
+    info = h.info()
+    arena = info["owned_bytes"]
+    assert arena > (4 << 20) and arena % (1 << 20) != 0  # (more chunks than stay on the device, and a short last one)
+    assert info["snapshot_device_bytes"] == {0: 0, 2: 2 << 20, 1 << 20: arena}[room_mb]
+    pa.pangulu_gstrf(h)
+    L1, U1 = pa.factors_as_scipy(h)
+    assert lib.pangulu_amd_reset_numeric(h.ref) == 0
+    assert lib.pangulu_amd_snapshot(h.ref) == 0  # (a second snapshot of the pristine records re-uses the first one's memory)
+    assert h.info()["snapshot_device_bytes"] == info["snapshot_device_bytes"]
+    pa.pangulu_gstrf(h)
+    L2, U2 = pa.factors_as_scipy(h)
+    pa.pangulu_finalize(h)
+    ref = factorize(mat, 128, oracle_library("r64"), ordering="nd")
+    for got, want in ((L1, ref["L"]), (U1, ref["U"]), (L2, ref["L"]), (U2, ref["U"])):
+        assert max_rel_diff(got, want) <= TOL["r64"]

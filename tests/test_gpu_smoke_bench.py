@@ -19,7 +19,7 @@ def test_smoke():
 
 def run_bench(*extra, timeout=1500):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "shell", "--size", "40", "40",
-                          "--steps", "2", "--warmup", "1"] + list(extra), capture_output=True, text=True, timeout=timeout)
+                          "--steps", "2", "--warmup", "1", "--full"] + list(extra), capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -102,7 +102,7 @@ def test_bench_on_a_matrix_file_without_coordinates(tmp_path):
     with open(rhs, "w") as f:
         f.write("%d\n" % n)
         f.write("\n".join("%.17g" % x for x in b) + "\n")
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     flops = []
     for extra in (["--mtx", mtx], ["--mtx", lid, "--rhs", rhs], ["--workload", "fem27", "--size", "14", "--no-coords"]):
         out = subprocess.run(base + extra, capture_output=True, text=True, timeout=900)
@@ -123,7 +123,7 @@ def test_bench_eight_ranks_on_one_gpu_and_multi_replay():
     replays the log of its first factorisation).  Eight ranks share 288 GB here, so the matrix is small; what is checked is the contract, not a rate."""
     for extra in (["--no-multi-replay"], []):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--workload", "fem27", "--size", "32", "--nb", "128",
-                              "--steps", "3", "--warmup", "2", "--cpu-sample-stride", "4"] + (extra or ["--cpu-ranks-leg"]), capture_output=True, text=True, timeout=1500)
+                              "--steps", "3", "--warmup", "2", "--full", "--cpu-sample-stride", "4"] + (extra or ["--cpu-ranks-leg"]), capture_output=True, text=True, timeout=1500)
         assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
         line = json.loads([ln for ln in out.stdout.strip().splitlines() if ln.startswith('{"metric"')][-1])
         for key in CONTRACT_KEYS:
@@ -177,7 +177,7 @@ def test_bench_gives_up_a_hanging_transport_inside_its_budget():
     env = dict(os.environ, PANGULU_BENCH_TEST_HANG_TRANSPORT="ipc")
     t0 = time.time()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "shell", "--size", "40", "40", "--steps", "2", "--warmup", "1",
-                          "--transport", "auto", "--worker-timeout", "25", "--total-budget", "400", "--cpu-sample-stride", "3", "--no-profile-pass"],
+                          "--full", "--transport", "auto", "--worker-timeout", "25", "--total-budget", "400", "--cpu-sample-stride", "3", "--no-profile-pass"],
                          capture_output=True, text=True, timeout=600, env=env)
     wall = time.time() - t0
     assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
@@ -189,3 +189,53 @@ def test_bench_gives_up_a_hanging_transport_inside_its_budget():
     assert line["config"]["transport"] == "host" and line["value"] > 0 and line["residual"] < 1e-10
     assert wall < 400 and line["bench_wall_s"] <= 400
     assert line["transport_ab"] is None  # (only behind a first attempt that succeeded)
+
+
+def test_plain_bench_run_and_dump_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` alone: N timed steps, the gate on their factors, the line -- nothing of what --full
+    adds.  --dump-outputs writes what the last timed step computed: the factors' entries and, through pangulu_gstrs, the solutions
+    for b = A 1 and for a seeded random right-hand side.  shell()'s rows are dominant by exactly 1 with negative off-diagonals, so
+    b = 1, ||inv(A)||_inf <= 1 and max |x - 1| <= ||A x - b||_inf <= ||A x - b||_2 = residual * sqrt(n); 1e-12 on top covers the
+    rounding of the residual's own product (row sums of |A| are below 200)."""
+    import numpy as np
+
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "shell", "--size", "40", "40", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
+    lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    for key in CONTRACT_KEYS:
+        assert key in line, key
+    assert line["steps"] == 3 and len(line["step_ms"]) == 3 and line["warmup"] == 1
+    assert abs(line["ms_per_step"] - sum(line["step_ms"]) / 3) <= 0.01 and line["value"] > 0
+    assert line["unit"] == "GFLOP/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["residual"] < 1e-10 and line["factor_check"] < 1e-12 and line["parity_failed"] is False
+    assert line["cpu_baseline"] is None and line["secondary"] is None and line["roofline"] is None and line["kernels"] == {}
+    assert line["ms_per_step_scheduler_in_loop"] is None and "scaling_prediction" not in line["model"]
+    arrays = {f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+    assert sorted(arrays) == ["L_values", "U_values", "x", "x_random"]
+    assert all(a.dtype == np.float64 and a.ndim == 1 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    n = line["config"]["n"]
+    assert arrays["x"].shape == (n,) and arrays["x_random"].shape == (n,)
+    assert np.abs(arrays["x"] - 1.0).max() <= line["residual"] * np.sqrt(n) + 1e-12
+    # The inputs are functions of the arguments alone, so the test can restate them: x_random solves A x = b for the seeded right-hand
+    # side (the residual bound the line itself is held to), and L_values / U_values are the entries, in column order, of the factors
+    # an independent factorisation of the same matrix leaves (TOL of tests/test_gpu_parity.py: 1e-12 of the largest entry).
+    import bench
+    from pangulu_amd import matrices as M
+
+    from .helpers import factorize
+
+    mat = M.shell(40, 40)
+    assert mat[0] == n
+    b_random = np.random.default_rng(bench.DUMP_SEED).uniform(-1.0, 1.0, n)
+    assert M.relative_residual(n, mat[1], mat[2], mat[3], arrays["x_random"], b_random) < 1e-10
+    ref = factorize(mat, line["config"]["nb"], "hip", ordering="nd", solve=False)
+    for name, F in (("L_values", ref["L"]), ("U_values", ref["U"])):
+        F = F.tocsc()
+        F.sort_indices()
+        assert arrays[name].shape == F.data.shape and F.nnz > n
+        assert np.abs(arrays[name] - F.data).max() <= 1e-12 * np.abs(F.data).max(), name

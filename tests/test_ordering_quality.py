@@ -76,6 +76,29 @@ def test_elastic3d_has_serenas_row_length():
     assert (P != P.T).nnz == 0
 
 
+@pytest.mark.parametrize("dofs", [3, 1, 2, 4])
+@pytest.mark.parametrize("size", [(1,), (2,), (3, 2, 1), (4, 1, 3), (5, 7, 2), (9,)], ids=str)
+def test_elastic3d_is_the_assembled_matrix_entry_for_entry(size, dofs):
+    """elastic3d writes its CSC arrays directly (the bench matrix has 60 M entries); they are bit for bit those of the assembly
+    its definition reads as, the one shell() uses: node graph + identity, a full dofs x dofs block per node pair, off-diagonal
+    -(1 + ((7 i + 13 j) mod 5) / 4), diagonal = sum of the row's magnitudes + 1 -- on grids with fewer than three layers too."""
+    import numpy as np
+    import scipy.sparse as sp
+
+    nx, ny, nz = (size * 3)[:3] if len(size) == 1 else size
+    off = [(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1) if abs(a) + abs(b) + abs(c) in (1, 3)]
+    K = sp.kron(M._stencil(nx, ny, nz, off) + sp.identity(nx * ny * nz, format="csc"), np.ones((dofs, dofs)), format="coo")
+    i, j = K.row.astype(np.int64), K.col.astype(np.int64)
+    i, j = i[i != j], j[i != j]
+    A = sp.csc_matrix((-(1.0 + 0.25 * ((i * 7 + j * 13) % 5)), (i, j)), shape=K.shape)
+    A = A + sp.diags(np.asarray(abs(A).sum(axis=1)).ravel() + 1.0, format="csc")
+    want = M._finish(A, np.float64, np.repeat(M._grid_coords(nx, ny, nz), dofs, axis=0))
+    got = M.elastic3d(*size, dofs=dofs)
+    assert got[0] == want[0]
+    for g, w in zip(got[1:], want[1:]):
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w)
+
+
 def test_unknowns_of_one_node_are_dissected_together(tlib):
     """Several unknowns per mesh node (elastic3d: 3, every unknown of a node coupled to the same neighbours): the graph-only dissection
     collapses indistinguishable vertices before it looks for separators (METIS_NodeND's `compress`), so that a refinement move

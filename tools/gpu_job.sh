@@ -86,6 +86,7 @@ repeat)
     echo "[gpu_job repeat] $N of $N passed" | tee -a gpurun_out/${TAG}_repeat.log
     ;;
 launchlog)
+    set -- --full "$@"  # (the log is of the profile pass, which a plain bench.py run does not make)
     PANGULU_HIP_LAUNCH_LOG=$R/gpurun_out/${TAG}_launch_log.txt timeout 900 python3 bench.py --no-cpu-baseline --no-secondary --no-sched-steps --steps 2 --warmup 1 "$@" \
         > gpurun_out/${TAG}_bench.json.log 2> gpurun_out/${TAG}_bench.err
     python3 tools/launch_log_summary.py gpurun_out/${TAG}_launch_log.txt | tee gpurun_out/${TAG}_launch_log_summary.txt
