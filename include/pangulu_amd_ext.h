@@ -146,6 +146,20 @@ extern "C"
      * (pangulu_gstrf, pangulu_amd_get_info, pangulu_amd_rank_model). */
     int pangulu_amd_model_for_ranks(void **pangulu_handle, int nranks, double *out12);
 
+    /* ---- several right-hand sides ---------------------------------------------------------------------- */
+    /* Solves A X = B for nrhs right-hand sides with the factors of the last pangulu_gstrf.  `rhs` is column-major, column j at
+     * rhs + j*ldb, ldb >= n (rank 0; ignored elsewhere); overwritten with X.  Permutation, padding rows and the scaling of a
+     * pangulu_amd_set_scaling(1) handle are applied per column exactly as pangulu_gstrs applies them.  Collective: every rank
+     * calls it; rank 0's rhs, nrhs and ldb decide.  On one rank with the factors on the device the columns are swept in
+     * panels of up to 16 (the factor records are read once per panel, not once per column); otherwise -- several ranks,
+     * PANGULU_AMD_DEVICE_SOLVE=0 -- the sweep of pangulu_gstrs runs once per column.  info.time_solve covers the whole call.
+     * Returns 0 (nrhs == 0: nothing to do); 1 if the handle has not been factorised; 2 if ldb < n or rhs == NULL on rank 0. */
+    int pangulu_amd_gstrs_multi(sparse_value_t *rhs, sparse_index_t nrhs, sparse_pointer_t ldb, pangulu_gstrs_options *gstrs_options,
+                                void **pangulu_handle);
+    /* what the last pangulu_amd_gstrs_multi on this handle did: columns swept on the device (0: host sweep), panel width used
+     * (the widest panel; 1: column by column), number of panels.  Any pointer may be NULL.  Returns 0. */
+    int pangulu_amd_last_solve_path(void **pangulu_handle, int *device_columns, int *panel_width, int *panels);
+
     /* ---- repeated factorisations (bench.py) ---------------------------------------------------------- */
     /* gstrf overwrites the matrix with its factors.  snapshot() keeps a pristine device-side copy of this rank's
      * block records (call it after pangulu_init, before the first gstrf); reset_numeric() restores the records

@@ -308,6 +308,22 @@ extern "C"
     void pangulu_platform_0201001_block_trsv(pangulu_inblock_idx nb, int upper, pangulu_uint64_t nlevel, const pangulu_uint64_t *level_ptr,
                                              const pangulu_hip_solve_row_t *rows, pangulu_storage_slot_t *const *blk_slots,
                                              const pangulu_exblock_idx *blk_bcol, calculate_type *x, pangulu_uint64_t xlen);
+    /* Optional: the same two sweeps for panels of right-hand sides (pangulu_amd_gstrs_multi on one rank): every factor entry is
+     * read once per panel and applied to the panel's w values.  One sweep is described as for block_trsv; both descriptions
+     * (the lower sweep, then the upper one) are uploaded once per call and serve all `npanel` panels.  `X` is a HOST buffer
+     * holding the panels one after the other; panel p has xlen x w[p] values with the right-hand side fastest
+     * (X_p[i * w[p] + r]), w[p] a power of two, and is overwritten with U^-1 L^-1 X_p.  Returns the widest panel the kernels
+     * take at this nb (a power of two <= 16; 1: none, the caller loops block_trsv over the columns); npanel = 0 only asks. */
+    typedef struct pangulu_hip_solve_sweep_t
+    {
+        pangulu_uint64_t nlevel;
+        const pangulu_uint64_t *level_ptr;
+        const pangulu_hip_solve_row_t *rows;
+        pangulu_storage_slot_t *const *blk_slots;
+        const pangulu_exblock_idx *blk_bcol;
+    } pangulu_hip_solve_sweep_t;
+    int pangulu_platform_0201001_block_trsm_multi(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *lower, const pangulu_hip_solve_sweep_t *upper,
+                                                  calculate_type *X, pangulu_uint64_t xlen, pangulu_uint64_t npanel, const int *w);
     /* Optional: y[dst segment] += A_blk * x[src segment] for a list of device-resident block records, in one launch (one
      * workgroup per block, floating-point atomics on y).  `x` and `y` are HOST vectors of `xlen` values (nb per block
      * row / column); y is read, updated and written back.  csr[i] != 0: the record is an upper diagonal half (CSR, diagonal

@@ -79,6 +79,7 @@ void bind_builtin_hip(Platform &p)
     p.marker_done = pangulu_platform_0201001_marker_done;
     p.marker_wait = pangulu_platform_0201001_marker_wait;
     p.block_trsv = pangulu_platform_0201001_block_trsv;
+    p.block_trsm_multi = pangulu_platform_0201001_block_trsm_multi;
     p.block_spmv_add = pangulu_platform_0201001_block_spmv_add;
     p.schedule = pangulu_platform_0201001_schedule;
     p.schedule_range = pangulu_platform_0201001_schedule_range;
@@ -132,6 +133,45 @@ struct NearDevice
             plat.bind_near_device(0);
     }
 };
+
+// What pangulu_gstrs does to one right-hand side on rank 0 before and after the sweeps: the symmetric permutation with its padding
+// rows and, on a handle with scaling on, the row scaling of b going in and the matching + column scaling of x coming out.
+inline val_t value_times(val_t v, double s)
+{
+#ifdef PANGULU_COMPLEX
+    return val_t{(calculate_real_type)(v.re * s), (calculate_real_type)(v.im * s)};
+#else
+    return (val_t)(v * s);
+#endif
+}
+void rhs_to_factor_space(const Solver &S, const val_t *rhs, val_t *b)
+{
+    const bool scaled = !S.scale_row.empty();
+    for (u32 i = 0; i < S.n; i++)
+    {
+        if (S.perm[i] < S.n_user)
+            b[i] = scaled ? value_times(rhs[S.perm[i]], S.scale_row[S.perm[i]]) : rhs[S.perm[i]]; // A1 y = Dr b
+        else
+            memset(&b[i], 0, sizeof(val_t)); // padding row: 1 * x = 0
+    }
+}
+void solution_from_factor_space(const Solver &S, const val_t *b, val_t *rhs)
+{
+    if (S.scale_row.empty())
+    {
+        for (u32 i = 0; i < S.n; i++)
+            if (S.perm[i] < S.n_user)
+                rhs[S.perm[i]] = b[i];
+        return;
+    }
+    // y (in the scaled matrix's column order) -> x[q(i)] = dc[q(i)] y[i]
+    std::vector<val_t> y(S.n_user);
+    for (u32 i = 0; i < S.n; i++)
+        if (S.perm[i] < S.n_user)
+            y[S.perm[i]] = b[i];
+    for (u32 i = 0; i < S.n_user; i++)
+        rhs[S.match_col[i]] = value_times(y[i], S.scale_col[S.match_col[i]]);
+}
 } // namespace
 
 extern "C"
@@ -665,49 +705,65 @@ extern "C"
         NearDevice near(active_platform());
         Comm *comm = world();
         std::vector<val_t> b(S->n);
-        const bool scaled = !S->scale_row.empty();
-        auto times = [](val_t v, double s) -> val_t
-        {
-#ifdef PANGULU_COMPLEX
-            return val_t{(calculate_real_type)(v.re * s), (calculate_real_type)(v.im * s)};
-#else
-            return (val_t)(v * s);
-#endif
-        };
         if (comm->rank == 0)
-        {
-            for (u32 i = 0; i < S->n; i++)
-            {
-                if (S->perm[i] < S->n_user)
-                    b[i] = scaled ? times(rhs[S->perm[i]], S->scale_row[S->perm[i]]) : rhs[S->perm[i]]; // A1 y = Dr b
-                else
-                    memset(&b[i], 0, sizeof(val_t)); // padding row: 1 * x = 0
-            }
-        }
+            rhs_to_factor_space(*S, rhs, b.data());
         comm->bcast(b.data(), sizeof(val_t) * S->n, 0);
         comm->barrier();
         double t0 = wall_seconds();
         triangular_solve(*S, b.data());
         S->info.time_solve = wall_seconds() - t0;
         if (comm->rank == 0)
+            solution_from_factor_space(*S, b.data(), rhs);
+    }
+
+    int pangulu_amd_gstrs_multi(sparse_value_t *rhs, sparse_index_t nrhs, sparse_pointer_t ldb, pangulu_gstrs_options *gstrs_options, void **pangulu_handle)
+    {
+        if (gstrs_options == nullptr)
         {
-            if (!scaled)
-            {
-                for (u32 i = 0; i < S->n; i++)
-                    if (S->perm[i] < S->n_user)
-                        rhs[S->perm[i]] = b[i];
-            }
-            else
-            {
-                // y (in the scaled matrix's column order) -> x[q(i)] = dc[q(i)] y[i]
-                std::vector<val_t> y(S->n_user);
-                for (u32 i = 0; i < S->n; i++)
-                    if (S->perm[i] < S->n_user)
-                        y[S->perm[i]] = b[i];
-                for (u32 i = 0; i < S->n_user; i++)
-                    rhs[S->match_col[i]] = times(y[i], S->scale_col[S->match_col[i]]);
-            }
+            if (world()->rank == 0)
+                printf("[PanguLU ERROR] Invalid input parameter. gstrs option struct pointer is NULL. Exit.\n");
+            exit(1);
         }
+        Solver *S = (Solver *)*pangulu_handle;
+        if (!S->factored)
+            return 1;
+        const double t0 = wall_seconds();
+        NearDevice near(active_platform());
+        Comm *comm = world();
+        // rank 0's arguments decide for everybody
+        unsigned long long head[2] = {0, (unsigned long long)nrhs};
+        if (comm->rank == 0 && nrhs != 0 && (rhs == nullptr || ldb < (sparse_pointer_t)S->n_user))
+            head[0] = 2;
+        comm->bcast(head, sizeof(head), 0);
+        if (head[0] != 0)
+            return (int)head[0];
+        nrhs = (sparse_index_t)head[1];
+        if (nrhs == 0)
+            return 0;
+        std::vector<val_t> b((size_t)S->n * nrhs);
+        if (comm->rank == 0)
+            for (sparse_index_t j = 0; j < nrhs; j++)
+                rhs_to_factor_space(*S, rhs + (size_t)j * ldb, b.data() + (size_t)j * S->n);
+        comm->bcast(b.data(), sizeof(val_t) * b.size(), 0);
+        comm->barrier();
+        triangular_solve_multi(*S, b.data(), (u32)nrhs);
+        if (comm->rank == 0)
+            for (sparse_index_t j = 0; j < nrhs; j++)
+                solution_from_factor_space(*S, b.data() + (size_t)j * S->n, rhs + (size_t)j * ldb);
+        S->info.time_solve = wall_seconds() - t0;
+        return 0;
+    }
+
+    int pangulu_amd_last_solve_path(void **pangulu_handle, int *device_columns, int *panel_width, int *panels)
+    {
+        Solver *S = (Solver *)*pangulu_handle;
+        if (device_columns)
+            *device_columns = S->last_solve_device_columns;
+        if (panel_width)
+            *panel_width = S->last_solve_panel_width;
+        if (panels)
+            *panels = S->last_solve_panels;
+        return 0;
     }
 
     void pangulu_gssv(sparse_value_t *rhs, pangulu_gstrf_options *gstrf_options, pangulu_gstrs_options *gstrs_options, void **pangulu_handle)

@@ -81,6 +81,8 @@ struct Platform
     void *(*marker_record_replay)() = nullptr;
     void (*block_spmv_add)(pangulu_inblock_idx, pangulu_uint64_t, slot_t *const *, const pangulu_exblock_idx *, const pangulu_exblock_idx *, const int *,
                            const val_t *, val_t *, pangulu_uint64_t) = nullptr;
+    int (*block_trsm_multi)(pangulu_inblock_idx, const pangulu_hip_solve_sweep_t *, const pangulu_hip_solve_sweep_t *, val_t *, pangulu_uint64_t,
+                            pangulu_uint64_t, const int *) = nullptr;
 };
 Platform &active_platform();               // built-in HIP unless the test hook replaced it
 bool platform_is_builtin_hip();
@@ -304,6 +306,18 @@ struct StructureModel
     u64 critical_path_tasks = 0;
 };
 
+// One sweep of the level-scheduled device solve (pg_sptrsv.cpp): the block rows grouped by level of the block dependency
+// graph and their off-diagonal blocks on the sweep's side, as pangulu_platform_0201001_block_trsv takes them.  A pure function
+// of the block pattern and of where the records live.
+struct SolveSweepPlan
+{
+    u32 nlevel = 0;
+    std::vector<pangulu_uint64_t> level_ptr;
+    std::vector<pangulu_hip_solve_row_t> rows;
+    std::vector<slot_t *> blk_slots;
+    std::vector<pangulu_exblock_idx> blk_bcol;
+};
+
 struct Solver
 {
     // configuration
@@ -341,6 +355,11 @@ struct Solver
     u64 pending_total = 0;
     bool factored = false, host_values_current = true;
     bool schedule_recorded = false;        // the back-end holds the launch list of this handle's factorisation (one rank)
+    // pangulu_amd_gstrs_multi, device path: both sweeps' plans, built on first use (new values on the same pattern keep them:
+    // the records stay where they are); and what the last call did (pangulu_amd_last_solve_path)
+    SolveSweepPlan solve_plan[2];
+    bool solve_plan_ready = false;
+    int last_solve_device_columns = 0, last_solve_panel_width = 0, last_solve_panels = 0;
     // Multi-rank replay (round 4, PANGULU_AMD_MULTI_REPLAY=1): what THIS rank did in its first factorisation, in order -- the ranges
     // of the back-end's recorded operations its platform calls produced, the markers between them with the blocks that were
     // announced behind each, and which blocks of other ranks had arrived (into which receive slot) before each call was made.
@@ -423,6 +442,7 @@ void numeric_factorize(Solver &S);                        // the hot path
 void record_schedule(Solver &S);                          // pangulu_init, one rank: dry run of the scheduler, the back-end records the launch list
 void download_factors(Solver &S);                         // device -> host mirror of owned values
 void triangular_solve(Solver &S, val_t *rhs_permuted);    // forward + backward block sweeps (host kernels)
+void triangular_solve_multi(Solver &S, val_t *B, u32 nrhs); // the same for n x nrhs permuted values, column j at B + j n: panels on the device, or the sweep above per column
 double factor_check(Solver &S);                           // ||L(U 1) - A 1|| / ||A 1|| on the factors where they are (pg_check.cpp; collective)
 double factor_check_vectors(Solver &S, int nvec, unsigned long long seed); // the same on the ones vector + nvec - 1 random +-1 vectors: the worst quotient
 void compute_task_model(Solver &S, double hbm_bytes_per_s, double fp_flops_per_s); // pg_model.cpp: T* of SURVEY.md §8d

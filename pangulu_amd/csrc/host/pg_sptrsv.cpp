@@ -73,67 +73,82 @@ void block_upper_solve(u32 nb, const slot_t *u, val_t *x)
 
 } // namespace
 
+// The level structure of one sweep of the device solve: a pure function of the block pattern (and of the slots the records sit in).
+static void build_sweep_plan(const Solver &S, bool lower, SolveSweepPlan &plan)
+{
+    const BlockPattern &P = S.pat;
+    const u32 nbk = S.nbk;
+    // level of a block row = 1 + the highest level among the rows its off-diagonal blocks (on the sweep's side) read
+    std::vector<u32> level(nbk, 0);
+    u32 nlevel = 0;
+    for (u32 step = 0; step < nbk; step++)
+    {
+        const u32 brow = lower ? step : nbk - 1 - step;
+        const u64 rb = lower ? P.rowptr[brow] : P.first_after_diag_csr[brow];
+        const u64 re = lower ? P.first_after_diag_csr[brow] : P.rowptr[brow + 1];
+        u32 lv = 0;
+        for (u64 r = rb; r < re; r++)
+            lv = std::max(lv, level[P.colidx[r]] + 1);
+        level[brow] = lv;
+        nlevel = std::max(nlevel, lv + 1);
+    }
+    plan.nlevel = nlevel;
+    plan.level_ptr.assign((size_t)nlevel + 1, 0);
+    for (u32 k = 0; k < nbk; k++)
+        plan.level_ptr[level[k] + 1]++;
+    for (u32 l = 0; l < nlevel; l++)
+        plan.level_ptr[l + 1] += plan.level_ptr[l];
+    plan.rows.assign(nbk, pangulu_hip_solve_row_t());
+    plan.blk_slots.clear();
+    plan.blk_bcol.clear();
+    std::vector<pangulu_uint64_t> cur(plan.level_ptr.begin(), plan.level_ptr.end() - 1);
+    for (u32 brow = 0; brow < nbk; brow++)
+    {
+        pangulu_hip_solve_row_t R;
+        R.brow = brow;
+        R.first = plan.blk_slots.size();
+        R.diag = lower ? S.diag_lower[brow] : S.diag_upper[brow];
+        const u64 rb = lower ? P.rowptr[brow] : P.first_after_diag_csr[brow];
+        const u64 re = lower ? P.first_after_diag_csr[brow] : P.rowptr[brow + 1];
+        for (u64 r = rb; r < re; r++)
+        {
+            plan.blk_slots.push_back(S.slot_of[P.csr_to_csc[r]]);
+            plan.blk_bcol.push_back(P.colidx[r]);
+        }
+        R.nblk = (pangulu_exblock_idx)(plan.blk_slots.size() - R.first);
+        plan.rows[cur[level[brow]]++] = R;
+    }
+    if (plan.blk_slots.empty())
+    {
+        plan.blk_slots.push_back(nullptr);
+        plan.blk_bcol.push_back(0);
+    }
+}
+
+// one rank, a device platform, PANGULU_AMD_DEVICE_SOLVE not 0
+static bool device_solve_enabled(const Solver &S, const Platform &plat)
+{
+    const char *e = getenv("PANGULU_AMD_DEVICE_SOLVE");
+    return !(S.nproc != 1 || plat.host_memory || !plat.block_trsv || (e && atoi(e) == 0));
+}
+
 // Single rank on a device: both sweeps on the device-resident factors (no download of the factors), level by level of the
 // block dependency graph -- pangulu_platform_0201001_block_trsv.  PANGULU_AMD_DEVICE_SOLVE=0 keeps the host sweep.
 static bool device_solve(Solver &S, val_t *rhs)
 {
     Platform &plat = active_platform();
-    const char *e = getenv("PANGULU_AMD_DEVICE_SOLVE");
-    if (S.nproc != 1 || plat.host_memory || !plat.block_trsv || (e && atoi(e) == 0))
+    if (!device_solve_enabled(S, plat))
         return false;
-    const BlockPattern &P = S.pat;
     const u32 nb = S.nb, nbk = S.nbk;
     std::vector<val_t> x((size_t)nbk * nb, vmake(0));
     std::copy(rhs, rhs + S.n, x.begin());
     for (int pass = 0; pass < 2; pass++)
     {
         const bool lower = pass == 0;
-        // level of a block row = 1 + the highest level among the rows its off-diagonal blocks (on the sweep's side) read
-        std::vector<u32> level(nbk, 0);
-        u32 nlevel = 0;
-        for (u32 step = 0; step < nbk; step++)
-        {
-            const u32 brow = lower ? step : nbk - 1 - step;
-            const u64 rb = lower ? P.rowptr[brow] : P.first_after_diag_csr[brow];
-            const u64 re = lower ? P.first_after_diag_csr[brow] : P.rowptr[brow + 1];
-            u32 lv = 0;
-            for (u64 r = rb; r < re; r++)
-                lv = std::max(lv, level[P.colidx[r]] + 1);
-            level[brow] = lv;
-            nlevel = std::max(nlevel, lv + 1);
-        }
-        std::vector<pangulu_uint64_t> level_ptr((size_t)nlevel + 1, 0);
-        for (u32 k = 0; k < nbk; k++)
-            level_ptr[level[k] + 1]++;
-        for (u32 l = 0; l < nlevel; l++)
-            level_ptr[l + 1] += level_ptr[l];
-        std::vector<pangulu_hip_solve_row_t> rows(nbk);
-        std::vector<slot_t *> blk_slots;
-        std::vector<pangulu_exblock_idx> blk_bcol;
-        std::vector<pangulu_uint64_t> cur(level_ptr.begin(), level_ptr.end() - 1);
-        for (u32 brow = 0; brow < nbk; brow++)
-        {
-            pangulu_hip_solve_row_t R;
-            R.brow = brow;
-            R.first = blk_slots.size();
-            R.diag = lower ? S.diag_lower[brow] : S.diag_upper[brow];
-            const u64 rb = lower ? P.rowptr[brow] : P.first_after_diag_csr[brow];
-            const u64 re = lower ? P.first_after_diag_csr[brow] : P.rowptr[brow + 1];
-            for (u64 r = rb; r < re; r++)
-            {
-                blk_slots.push_back(S.slot_of[P.csr_to_csc[r]]);
-                blk_bcol.push_back(P.colidx[r]);
-            }
-            R.nblk = (pangulu_exblock_idx)(blk_slots.size() - R.first);
-            rows[cur[level[brow]]++] = R;
-        }
-        if (blk_slots.empty())
-        {
-            blk_slots.push_back(nullptr);
-            blk_bcol.push_back(0);
-        }
-        plat.block_trsv((pangulu_inblock_idx)nb, lower ? 0 : 1, nlevel, level_ptr.data(), rows.data(), blk_slots.data(), blk_bcol.data(), x.data(),
-                        (pangulu_uint64_t)x.size());
+        SolveSweepPlan plan;
+        build_sweep_plan(S, lower, plan);
+        plat.block_trsv((pangulu_inblock_idx)nb, lower ? 0 : 1, plan.nlevel, plan.level_ptr.data(), plan.rows.data(), plan.blk_slots.data(),
+                        plan.blk_bcol.data(), x.data(), (pangulu_uint64_t)x.size());
     }
     std::copy(x.begin(), x.begin() + S.n, rhs);
     return true;
@@ -207,6 +222,93 @@ void triangular_solve(Solver &S, val_t *rhs)
         comm->barrier();
     }
     std::copy(x.begin(), x.begin() + S.n, rhs);
+}
+
+// Panels of right-hand sides through pangulu_platform_0201001_block_trsm_multi where device_solve() would run, the sweep above
+// column by column everywhere else (N > 1 ranks, host-memory platforms, PANGULU_AMD_DEVICE_SOLVE=0): collective, same tags.
+void triangular_solve_multi(Solver &S, val_t *Bm, u32 nrhs)
+{
+    Platform &plat = active_platform();
+    S.last_solve_device_columns = 0;
+    S.last_solve_panel_width = 1;
+    S.last_solve_panels = (int)nrhs;
+    if (!device_solve_enabled(S, plat) || !plat.block_trsm_multi)
+    {
+        for (u32 j = 0; j < nrhs; j++)
+            triangular_solve(S, Bm + (size_t)j * S.n);
+        return;
+    }
+    S.last_solve_device_columns = (int)nrhs;
+    const u32 nb = S.nb, n = S.n;
+    const int wmax = plat.block_trsm_multi((pangulu_inblock_idx)nb, nullptr, nullptr, nullptr, 0, 0, nullptr);
+    if (wmax < 2)
+    {
+        // nb too large for even two columns' tiles in LDS: the single-vector device sweep per column
+        for (u32 j = 0; j < nrhs; j++)
+            triangular_solve(S, Bm + (size_t)j * n);
+        return;
+    }
+    if (!S.solve_plan_ready)
+    {
+        build_sweep_plan(S, true, S.solve_plan[0]);
+        build_sweep_plan(S, false, S.solve_plan[1]);
+        S.solve_plan_ready = true;
+    }
+    // panels: the widest width while that many columns are left, then the smallest power of two that holds the rest (zero columns pad it)
+    std::vector<int> w;
+    size_t total_w = 0;
+    for (u32 left = nrhs; left;)
+    {
+        int wp = 1;
+        while (wp < wmax && (u32)wp < left)
+            wp <<= 1;
+        w.push_back(wp);
+        total_w += (size_t)wp;
+        left -= std::min(left, (u32)wp);
+    }
+    const size_t xlen = (size_t)S.nbk * nb;
+    std::vector<val_t> X(xlen * total_w, vmake(0));
+    auto each_panel = [&](auto &&f)
+    {
+        size_t off = 0;
+        u32 j0 = 0;
+        for (int wp : w)
+        {
+            const u32 nc = std::min((u32)wp, nrhs - j0);
+            f(X.data() + off, wp, j0, nc);
+            off += xlen * (size_t)wp;
+            j0 += nc;
+        }
+    };
+    each_panel([&](val_t *Xp, int wp, u32 j0, u32 nc)
+               {
+                   for (u32 r = 0; r < nc; r++)
+                   {
+                       const val_t *col = Bm + (size_t)(j0 + r) * n;
+                       for (u32 i = 0; i < n; i++)
+                           Xp[(size_t)i * wp + r] = col[i];
+                   } });
+    pangulu_hip_solve_sweep_t sw[2];
+    for (int s = 0; s < 2; s++)
+    {
+        const SolveSweepPlan &pl = S.solve_plan[s];
+        sw[s].nlevel = pl.nlevel;
+        sw[s].level_ptr = pl.level_ptr.data();
+        sw[s].rows = pl.rows.data();
+        sw[s].blk_slots = pl.blk_slots.data();
+        sw[s].blk_bcol = pl.blk_bcol.data();
+    }
+    plat.block_trsm_multi((pangulu_inblock_idx)nb, &sw[0], &sw[1], X.data(), (pangulu_uint64_t)xlen, (pangulu_uint64_t)w.size(), w.data());
+    each_panel([&](val_t *Xp, int wp, u32 j0, u32 nc)
+               {
+                   for (u32 r = 0; r < nc; r++)
+                   {
+                       val_t *col = Bm + (size_t)(j0 + r) * n;
+                       for (u32 i = 0; i < n; i++)
+                           col[i] = Xp[(size_t)i * wp + r];
+                   } });
+    S.last_solve_panel_width = w[0];
+    S.last_solve_panels = (int)w.size();
 }
 
 } // namespace pg

@@ -800,8 +800,46 @@ namespace
 {
 
 #include "pg_hip_block_solve.h"
+#include "pg_hip_block_solve_multi.h"
 
 #include "pg_hip_backend.h"
+
+// device-side descriptors of one sweep (block_trsv's arguments), appended to hr / hb: rows keep their order, the blocks of level l
+// are hb[blk_level_ptr[l] .. blk_level_ptr[l + 1]) counted from the first block appended here
+void append_solve_descriptors(int upper, pangulu_uint64_t nlevel, const pangulu_uint64_t *level_ptr, const pangulu_hip_solve_row_t *rows,
+                              pangulu_storage_slot_t *const *blk_slots, const pangulu_exblock_idx *blk_bcol, std::vector<SolveRowD> &hr,
+                              std::vector<SolveBlkD> &hb, std::vector<size_t> &blk_level_ptr)
+{
+    const size_t r0 = hr.size(), b0 = hb.size();
+    hr.resize(r0 + (size_t)level_ptr[nlevel]);
+    blk_level_ptr.assign((size_t)nlevel + 1, 0);
+    for (size_t l = 0; l < (size_t)nlevel; l++)
+    {
+        for (size_t r = (size_t)level_ptr[l]; r < (size_t)level_ptr[l + 1]; r++)
+        {
+            const slot_t *d = rows[r].diag;
+            SolveRowD &R = hr[r0 + r];
+            R.brow = rows[r].brow;
+            R.nblk = rows[r].nblk;
+            R.first = hb.size() - b0;
+            R.dptr = upper ? d->d_rowpointer : d->d_columnpointer;
+            R.didx = upper ? d->d_columnindex : d->d_rowindex;
+            R.dval = d->d_value;
+            for (size_t b = 0; b < rows[r].nblk; b++)
+            {
+                const slot_t *sb = blk_slots[rows[r].first + b];
+                SolveBlkD D;
+                D.cp = sb->d_columnpointer;
+                D.ri = sb->d_rowindex;
+                D.val = sb->d_value;
+                D.bcol = blk_bcol[rows[r].first + b];
+                D.brow = rows[r].brow;
+                hb.push_back(D);
+            }
+        }
+        blk_level_ptr[l + 1] = hb.size() - b0;
+    }
+}
 
 const double SV = (double)sizeof(val_t);
 
@@ -1515,37 +1553,14 @@ extern "C"
         HIP_CHECK(hipSetDevice(B.device));
         join_records(B.stream); // the sparse records of finished blocks are written on the records stream
         join_background(B.stream);
-        const size_t nrow = (size_t)level_ptr[nlevel];
-        size_t nblk = 0;
-        for (size_t r = 0; r < nrow; r++)
-            nblk += rows[r].nblk;
-        std::vector<SolveRowD> hr(std::max<size_t>(nrow, 1));
-        std::vector<SolveBlkD> hb(std::max<size_t>(nblk, 1));
-        std::vector<size_t> blk_level_ptr((size_t)nlevel + 1, 0);
-        size_t o = 0;
-        for (size_t l = 0; l < (size_t)nlevel; l++)
-        {
-            for (size_t r = (size_t)level_ptr[l]; r < (size_t)level_ptr[l + 1]; r++)
-            {
-                const slot_t *d = rows[r].diag;
-                hr[r].brow = rows[r].brow;
-                hr[r].nblk = rows[r].nblk;
-                hr[r].first = o;
-                hr[r].dptr = upper ? d->d_rowpointer : d->d_columnpointer;
-                hr[r].didx = upper ? d->d_columnindex : d->d_rowindex;
-                hr[r].dval = d->d_value;
-                for (size_t b = 0; b < rows[r].nblk; b++, o++)
-                {
-                    const slot_t *sb = blk_slots[rows[r].first + b];
-                    hb[o].cp = sb->d_columnpointer;
-                    hb[o].ri = sb->d_rowindex;
-                    hb[o].val = sb->d_value;
-                    hb[o].bcol = blk_bcol[rows[r].first + b];
-                    hb[o].brow = rows[r].brow;
-                }
-            }
-            blk_level_ptr[l + 1] = o;
-        }
+        std::vector<SolveRowD> hr;
+        std::vector<SolveBlkD> hb;
+        std::vector<size_t> blk_level_ptr;
+        append_solve_descriptors(upper, nlevel, level_ptr, rows, blk_slots, blk_bcol, hr, hb, blk_level_ptr);
+        if (hr.empty())
+            hr.resize(1);
+        if (hb.empty())
+            hb.resize(1);
         SolveRowD *d_rows = nullptr;
         SolveBlkD *d_blks = nullptr;
         val_t *d_x = nullptr;
@@ -1604,6 +1619,132 @@ extern "C"
         HIP_CHECK(hipFree(d_rows));
         HIP_CHECK(hipFree(d_blks));
         HIP_CHECK(hipFree(d_x));
+    }
+
+    // Both sweeps for panels of right-hand sides (see pg_hip_block_solve_multi.h).  The descriptors of both sweeps go up once; the
+    // panels then pass through one device buffer one after the other: upload, L sweep, U sweep, download.
+    int pangulu_platform_0201001_block_trsm_multi(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *lower, const pangulu_hip_solve_sweep_t *upper,
+                                                  calculate_type *X, pangulu_uint64_t xlen, pangulu_uint64_t npanel, const int *w)
+    {
+        // the widest panel: a tile row of at most 128 bytes (16 real values, 8 double-complex ones), and both kernels within the
+        // 96 KB of LDS the single-vector solve kernels allow themselves
+        const size_t budget = (size_t)96 << 10;
+        int wmax = (int)std::min<size_t>(16, 128 / sizeof(val_t));
+        while (wmax > 1 && (solve_multi_lds_gather(nb, wmax) > budget || solve_multi_chunk(nb, wmax, budget) < 1))
+            wmax >>= 1;
+        if (npanel == 0)
+            return wmax;
+        int wtop = 1;
+        for (size_t p = 0; p < (size_t)npanel; p++)
+        {
+            if (w[p] < 1 || w[p] > wmax || (w[p] & (w[p] - 1)))
+            {
+                fprintf(stderr, "[PanguLU-AMD ERROR] block_trsm_multi: panel width %d (nb = %d takes powers of two up to %d)\n", w[p], (int)nb, wmax);
+                exit(EXIT_FAILURE);
+            }
+            wtop = std::max(wtop, w[p]);
+        }
+        if (solve_multi_lds_gather(nb, 1) > budget || solve_multi_chunk(nb, 1, budget) < 1)
+        {
+            fprintf(stderr, "[PanguLU-AMD ERROR] block_trsm_multi: nb = %d does not fit the solve kernels' LDS\n", (int)nb);
+            exit(EXIT_FAILURE);
+        }
+        ensure_ready();
+        std::lock_guard<std::mutex> g(B.mutex);
+        flush_pending_getrf();
+        HIP_CHECK(hipSetDevice(B.device));
+        join_records(B.stream); // the sparse records of finished blocks are written on the records stream
+        join_background(B.stream);
+        const pangulu_hip_solve_sweep_t *sweep[2] = {lower, upper};
+        std::vector<SolveRowD> hr;
+        std::vector<SolveBlkD> hb;
+        std::vector<size_t> blk_level_ptr[2];
+        size_t row0[2], blk0[2];
+        for (int s = 0; s < 2; s++)
+        {
+            row0[s] = hr.size();
+            blk0[s] = hb.size();
+            append_solve_descriptors(s, sweep[s]->nlevel, sweep[s]->level_ptr, sweep[s]->rows, sweep[s]->blk_slots, sweep[s]->blk_bcol, hr, hb, blk_level_ptr[s]);
+        }
+        if (hr.empty())
+            hr.resize(1);
+        if (hb.empty())
+            hb.resize(1);
+        SolveRowD *d_rows = nullptr;
+        SolveBlkD *d_blks = nullptr;
+        val_t *d_x = nullptr;
+        HIP_CHECK(hipMalloc((void **)&d_rows, sizeof(SolveRowD) * hr.size()));
+        HIP_CHECK(hipMalloc((void **)&d_blks, sizeof(SolveBlkD) * hb.size()));
+        HIP_CHECK(hipMalloc((void **)&d_x, sizeof(val_t) * (size_t)xlen * (size_t)wtop));
+        HIP_CHECK(hipMemcpyAsync(d_rows, hr.data(), sizeof(SolveRowD) * hr.size(), hipMemcpyHostToDevice, B.stream));
+        HIP_CHECK(hipMemcpyAsync(d_blks, hb.data(), sizeof(SolveBlkD) * hb.size(), hipMemcpyHostToDevice, B.stream));
+        auto run_panel = [&](auto wc)
+        {
+            constexpr int W = decltype(wc)::value;
+            const int ch = solve_multi_chunk(nb, W, budget);
+            const size_t lds_gather = solve_multi_lds_gather(nb, W), lds_level = solve_multi_lds_level(nb, W, ch);
+            static size_t allowed_gather = 0, allowed_level = 0; // (per W: the lambda is instantiated once per width)
+            if (lds_gather > allowed_gather)
+            {
+                HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_gather_multi_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gather));
+                allowed_gather = lds_gather;
+            }
+            if (lds_level > allowed_level)
+            {
+                HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_multi_kernel<false, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
+                HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_multi_kernel<true, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
+                allowed_level = lds_level;
+            }
+            for (int s = 0; s < 2; s++)
+                for (size_t l = 0; l < (size_t)sweep[s]->nlevel; l++)
+                {
+                    const pangulu_uint64_t *lp = sweep[s]->level_ptr;
+                    const size_t n = (size_t)(lp[l + 1] - lp[l]), nbl = blk_level_ptr[s][l + 1] - blk_level_ptr[s][l];
+                    if (!n)
+                        continue;
+                    if (nbl)
+                        hipLaunchKernelGGL(block_trsm_gather_multi_kernel<W>, dim3((unsigned)nbl), dim3(256), lds_gather, B.stream,
+                                           d_blks + blk0[s] + blk_level_ptr[s][l], (int)nb, d_x);
+                    if (s)
+                        hipLaunchKernelGGL((block_trsm_level_multi_kernel<true, W>), dim3((unsigned)n), dim3(256), lds_level, B.stream,
+                                           d_rows + row0[s] + lp[l], (int)nb, d_x, ch);
+                    else
+                        hipLaunchKernelGGL((block_trsm_level_multi_kernel<false, W>), dim3((unsigned)n), dim3(256), lds_level, B.stream,
+                                           d_rows + row0[s] + lp[l], (int)nb, d_x, ch);
+                }
+        };
+        val_t *Xp = X;
+        for (size_t p = 0; p < (size_t)npanel; p++)
+        {
+            const size_t bytes = sizeof(val_t) * (size_t)xlen * (size_t)w[p];
+            HIP_CHECK(hipMemcpyAsync(d_x, Xp, bytes, hipMemcpyHostToDevice, B.stream));
+            switch (w[p])
+            {
+            case 1:
+                run_panel(std::integral_constant<int, 1>());
+                break;
+            case 2:
+                run_panel(std::integral_constant<int, 2>());
+                break;
+            case 4:
+                run_panel(std::integral_constant<int, 4>());
+                break;
+            case 8:
+                run_panel(std::integral_constant<int, 8>());
+                break;
+            default:
+                run_panel(std::integral_constant<int, 16>());
+                break;
+            }
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(Xp, d_x, bytes, hipMemcpyDeviceToHost, B.stream));
+            Xp += (size_t)xlen * (size_t)w[p];
+        }
+        HIP_CHECK(hipStreamSynchronize(B.stream));
+        HIP_CHECK(hipFree(d_rows));
+        HIP_CHECK(hipFree(d_blks));
+        HIP_CHECK(hipFree(d_x));
+        return wmax;
     }
 
     void pangulu_platform_0201001_block_spmv_add(pangulu_inblock_idx nb, pangulu_uint64_t nblk, pangulu_storage_slot_t *const *slots,

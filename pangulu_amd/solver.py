@@ -100,6 +100,33 @@ def pangulu_gstrs(h, rhs):
     return x
 
 
+def pangulu_gstrs_multi(h, B, nrhs=None):
+    """Solves A X = B for all columns of B, shape (n, nrhs) in any memory order, with one pass over the factors per panel of
+    columns (pangulu_amd_gstrs_multi); returns X of the same shape (rank 0).  Other ranks pass None and nrhs."""
+    opt = _lib.GstrsOptions()
+    if B is not None:
+        B = np.asarray(B)
+        if B.ndim != 2 or B.shape[0] != h.n:
+            raise ValueError("B must have shape (%d, nrhs), got %r" % (h.n, B.shape))
+        x = np.array(B, dtype=h.dtype, order="F", copy=True)  # column j at x + j * n
+        nrhs = B.shape[1]
+        ptr = x.ctypes.data_as(ctypes.c_void_p)
+    else:
+        x, ptr = None, None
+    rc = h.lib.pangulu_amd_gstrs_multi(ptr, int(nrhs), h.n, ctypes.byref(opt), h.ref)
+    if rc != 0:
+        raise RuntimeError("pangulu_amd_gstrs_multi failed (%d): %s" % (rc, "the handle has not been factorised" if rc == 1 else "bad rhs / ldb"))
+    return x
+
+
+def last_solve_path(h):
+    """What the last pangulu_gstrs_multi on this handle did: columns swept on the device (0: host sweep), the widest panel, the
+    number of panels."""
+    d, w, p = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    h.lib.pangulu_amd_last_solve_path(h.ref, ctypes.byref(d), ctypes.byref(w), ctypes.byref(p))
+    return {"device_columns": int(d.value), "panel_width": int(w.value), "panels": int(p.value)}
+
+
 def pangulu_gssv(h, rhs):
     pangulu_gstrf(h)
     return pangulu_gstrs(h, rhs)

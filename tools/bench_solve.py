@@ -1,0 +1,84 @@
+"""One GPU, one handle: what a block of right-hand sides costs beside single pangulu_gstrs calls on the same factors.
+
+    python tools/bench_solve.py [--matrix elastic3d] [--size 48] [--nb 256] [--vtype r64] [--nrhs 1,4,16,64] [--repeats 5]
+
+After pangulu_gstrf it times, in this process, the median of `repeats` single pangulu_gstrs calls and the median of `repeats`
+pangulu_gstrs_multi calls per nrhs, and prints one JSON line: the times, the time per column, the panels, the factor bytes a panel
+streams (info.owned_bytes: every record is read once per panel) and the bandwidth that implies.  The yardstick is nrhs single
+calls.  (Run it through `tools/gpu_job.sh solve`, which puts it under a time limit.)"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+import pangulu_amd as pa  # noqa: E402
+from pangulu_amd import _lib, matrices as M  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--matrix", default="elastic3d", choices=["elastic3d", "fem27", "poisson3d", "shell", "kkt"])
+    ap.add_argument("--size", type=int, default=48)
+    ap.add_argument("--nb", type=int, default=256)
+    ap.add_argument("--vtype", default="r64", choices=sorted(_lib.VALUE_TYPES))
+    ap.add_argument("--nrhs", default="1,4,16,64")
+    ap.add_argument("--repeats", type=int, default=5)
+    a = ap.parse_args()
+    dt = _lib.VALUE_TYPES[a.vtype][0]
+    cplx = np.issubdtype(dt, np.complexfloating)
+    if a.matrix == "poisson3d":
+        mat = M.poisson3d(a.size, dtype=dt, shift=0.5j if cplx else 0.0)
+    elif a.matrix == "shell":
+        mat = M.shell(a.size, a.size, dtype=dt)
+    else:
+        mat = getattr(M, a.matrix)(a.size, dtype=dt)
+    n, cp, ri, va, co = mat
+    lib = _lib.load(a.vtype)
+    lib.pangulu_amd_reset_options()
+    h = pa.pangulu_init(n, len(va), cp, ri, va, nb=a.nb, vtype=a.vtype, coords=co, nthread=16)
+    t0 = time.time()
+    pa.pangulu_gstrf(h)
+    t_gstrf = time.time() - t0
+    info = h.info()
+    widths = [int(w) for w in a.nrhs.split(",")]
+    rng = np.random.default_rng(7)
+    B = rng.uniform(-1.0, 1.0, size=(n, max(widths))).astype(dt)
+    B[:, 0] = M.rhs_of_ones(n, cp, ri, va)
+
+    def median_of(f):
+        f()  # (warm-up: first-use allocations, the cached sweep plan)
+        ts = []
+        for _ in range(a.repeats):
+            t = time.time()
+            f()
+            ts.append(time.time() - t)
+        return statistics.median(ts)
+
+    b0 = np.ascontiguousarray(B[:, 0])
+    x_single = pa.pangulu_gstrs(h, b0)
+    t_single = median_of(lambda: pa.pangulu_gstrs(h, b0))
+    out = {"tool": "bench_solve", "matrix": "%s(%d)" % (a.matrix, a.size), "vtype": a.vtype, "n": n, "nb": a.nb, "gstrf_s": round(t_gstrf, 4),
+           "owned_bytes": int(info["owned_bytes"]), "gstrs_single_s": round(t_single, 5),
+           "gstrs_single_gbs": round(info["owned_bytes"] / t_single / 1e9, 1), "multi": []}
+    for w in widths:
+        Bw = np.asfortranarray(B[:, :w])
+        X = pa.pangulu_gstrs_multi(h, Bw)
+        path = pa.last_solve_path(h)
+        t = median_of(lambda: pa.pangulu_gstrs_multi(h, Bw))
+        res = max(M.relative_residual(n, cp, ri, va, X[:, j], Bw[:, j]) for j in range(w))
+        out["multi"].append({"nrhs": w, "seconds": round(t, 5), "seconds_per_column": round(t / w, 6), "speedup_vs_single_calls": round(t_single * w / t, 2),
+                             "device_columns": path["device_columns"], "panel_width": path["panel_width"], "panels": path["panels"],
+                             "factor_bytes_per_panel": int(info["owned_bytes"]), "implied_gbs": round(path["panels"] * info["owned_bytes"] / t / 1e9, 1),
+                             "worst_residual": float("%.2e" % res),
+                             "column0_vs_single": float("%.2e" % (np.abs(X[:, 0] - x_single).max() / np.abs(x_single).max()))})
+    pa.pangulu_finalize(h)
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -11,6 +11,7 @@
 #   micro <source.hip> [args]        build tools/microbench/<source.hip> on the box with hipcc and run it -> gpurun_out/<TAG>_micro.log
 #   repeat <n> <pytest node id>      the same test n times, stop at the first failure (start-up races) -> gpurun_out/<TAG>_repeat.log
 #   launchlog [bench.py flags]       per-launch log of the profiled factorisation + tools/launch_log_summary.py
+#   solve [bench_solve.py flags]     tools/bench_solve.py: block solves beside single pangulu_gstrs calls -> its JSON line on stdout
 #
 # TAG (environment, default "job") names the outputs.  Everything is written under gpurun_out/ (scratch; copy what is to be judged
 # into profiles/ and add its line to profiles/INDEX.md).
@@ -84,6 +85,10 @@ repeat)
         fi
     done
     echo "[gpu_job repeat] $N of $N passed" | tee -a gpurun_out/${TAG}_repeat.log
+    ;;
+solve)
+    timeout -k 10 ${SOLVE_TIMEOUT:-500} python3 tools/bench_solve.py "$@"
+    echo "[gpu_job solve] rc=$?"
     ;;
 launchlog)
     set -- --full "$@"  # (the log is of the profile pass, which a plain bench.py run does not make)
