@@ -293,12 +293,14 @@ extern "C"
     void *pangulu_platform_0201001_marker_record(void);
     int pangulu_platform_0201001_marker_done(void *marker);  /* 1 when everything before the marker has completed */
     void pangulu_platform_0201001_marker_wait(void *marker);
-    /* Optional: level-scheduled block triangular solve for pangulu_gstrs on one rank, on the device-resident factors (no
+    /* Optional: one sweep of the level-scheduled block triangular solve on one rank, on the device-resident factors (no
      * download): the reference makes one spmv / sptrsv platform call per block, on its CPU platform
-     * (src/pangulu_sptrsv.c:62,94,126,159); this call sweeps all levels of the block dependency graph, one launch per
+     * (src/pangulu_sptrsv.c:62,94,126,159); this call sweeps all levels of the block dependency graph, two launches per
      * level.  `x` is a HOST vector of `xlen` values, overwritten with the solution of the sweep (upper = 0: L, unit
      * diagonal; 1: U).  rows[level_ptr[l] .. level_ptr[l+1]) are the block rows of level l, `diag` their diagonal half
-     * (lower / upper), blk_slots / blk_bcol[first .. first + nblk) their off-diagonal blocks on the sweep's side. */
+     * (lower / upper), blk_slots / blk_bcol[first .. first + nblk) their off-diagonal blocks on the sweep's side.  The same
+     * kernels and launch code as one panel of width 1 in block_trsm_multi below, which the native host calls for pangulu_gstrs
+     * too (both sweeps in one call); this entry serves callers that want a single sweep. */
     typedef struct pangulu_hip_solve_row_t
     {
         pangulu_exblock_idx brow, nblk;
@@ -308,12 +310,13 @@ extern "C"
     void pangulu_platform_0201001_block_trsv(pangulu_inblock_idx nb, int upper, pangulu_uint64_t nlevel, const pangulu_uint64_t *level_ptr,
                                              const pangulu_hip_solve_row_t *rows, pangulu_storage_slot_t *const *blk_slots,
                                              const pangulu_exblock_idx *blk_bcol, calculate_type *x, pangulu_uint64_t xlen);
-    /* Optional: the same two sweeps for panels of right-hand sides (pangulu_amd_gstrs_multi on one rank): every factor entry is
-     * read once per panel and applied to the panel's w values.  One sweep is described as for block_trsv; both descriptions
-     * (the lower sweep, then the upper one) are uploaded once per call and serve all `npanel` panels.  `X` is a HOST buffer
-     * holding the panels one after the other; panel p has xlen x w[p] values with the right-hand side fastest
+    /* Optional: both sweeps for panels of right-hand sides (pangulu_gstrs: one panel of width 1; pangulu_amd_gstrs_multi): every
+     * factor entry is read once per panel and applied to the panel's w values.  One sweep is described as for block_trsv; both
+     * descriptions (the lower sweep, then the upper one) are uploaded once per call and serve all `npanel` panels.  `X` is a HOST
+     * buffer holding the panels one after the other; panel p has xlen x w[p] values with the right-hand side fastest
      * (X_p[i * w[p] + r]), w[p] a power of two, and is overwritten with U^-1 L^-1 X_p.  Returns the widest panel the kernels
-     * take at this nb (a power of two <= 16; 1: none, the caller loops block_trsv over the columns); npanel = 0 only asks. */
+     * take at this nb (a power of two <= 16; 1: single columns only -- nb too large for a wider tile in LDS, or
+     * PANGULU_HIP_SOLVE_CHUNKED=0 -- which this call sweeps like any other panel); npanel = 0 only asks. */
     typedef struct pangulu_hip_solve_sweep_t
     {
         pangulu_uint64_t nlevel;

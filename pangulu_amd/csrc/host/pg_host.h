@@ -307,7 +307,7 @@ struct StructureModel
 };
 
 // One sweep of the level-scheduled device solve (pg_sptrsv.cpp): the block rows grouped by level of the block dependency
-// graph and their off-diagonal blocks on the sweep's side, as pangulu_platform_0201001_block_trsv takes them.  A pure function
+// graph and their off-diagonal blocks on the sweep's side, as pangulu_platform_0201001_block_trsm_multi takes them.  A pure function
 // of the block pattern and of where the records live.
 struct SolveSweepPlan
 {
@@ -355,8 +355,8 @@ struct Solver
     u64 pending_total = 0;
     bool factored = false, host_values_current = true;
     bool schedule_recorded = false;        // the back-end holds the launch list of this handle's factorisation (one rank)
-    // pangulu_amd_gstrs_multi, device path: both sweeps' plans, built on first use (new values on the same pattern keep them:
-    // the records stay where they are); and what the last call did (pangulu_amd_last_solve_path)
+    // device solve (pangulu_gstrs and pangulu_amd_gstrs_multi on one rank): both sweeps' plans, built on first use (new values on the
+    // same pattern keep them: the records stay where they are); and what the last pangulu_amd_gstrs_multi did (pangulu_amd_last_solve_path)
     SolveSweepPlan solve_plan[2];
     bool solve_plan_ready = false;
     int last_solve_device_columns = 0, last_solve_panel_width = 0, last_solve_panels = 0;

@@ -132,32 +132,52 @@ static bool device_solve_enabled(const Solver &S, const Platform &plat)
     return !(S.nproc != 1 || plat.host_memory || !plat.block_trsv || (e && atoi(e) == 0));
 }
 
-// Single rank on a device: both sweeps on the device-resident factors (no download of the factors), level by level of the
-// block dependency graph -- pangulu_platform_0201001_block_trsv.  PANGULU_AMD_DEVICE_SOLVE=0 keeps the host sweep.
-static bool device_solve(Solver &S, val_t *rhs)
+// Single rank on a device: both sweeps on the device-resident factors (no download of the factors), level by level of the block
+// dependency graph.  X holds `npanel` panels one after the other, panel p with nbk*nb x w[p] values, right-hand side fastest: one
+// pangulu_platform_0201001_block_trsm_multi call; a platform with block_trsv alone takes single columns (w[p] = 1), sweep by sweep.
+// The plans of both sweeps are built on first use and kept on the handle.
+static void device_solve_panels(Solver &S, Platform &plat, val_t *X, size_t npanel, const int *w)
 {
-    Platform &plat = active_platform();
-    if (!device_solve_enabled(S, plat))
-        return false;
-    const u32 nb = S.nb, nbk = S.nbk;
-    std::vector<val_t> x((size_t)nbk * nb, vmake(0));
-    std::copy(rhs, rhs + S.n, x.begin());
-    for (int pass = 0; pass < 2; pass++)
+    if (!S.solve_plan_ready)
     {
-        const bool lower = pass == 0;
-        SolveSweepPlan plan;
-        build_sweep_plan(S, lower, plan);
-        plat.block_trsv((pangulu_inblock_idx)nb, lower ? 0 : 1, plan.nlevel, plan.level_ptr.data(), plan.rows.data(), plan.blk_slots.data(),
-                        plan.blk_bcol.data(), x.data(), (pangulu_uint64_t)x.size());
+        build_sweep_plan(S, true, S.solve_plan[0]);
+        build_sweep_plan(S, false, S.solve_plan[1]);
+        S.solve_plan_ready = true;
     }
-    std::copy(x.begin(), x.begin() + S.n, rhs);
-    return true;
+    pangulu_hip_solve_sweep_t sw[2];
+    for (int s = 0; s < 2; s++)
+    {
+        const SolveSweepPlan &pl = S.solve_plan[s];
+        sw[s].nlevel = pl.nlevel;
+        sw[s].level_ptr = pl.level_ptr.data();
+        sw[s].rows = pl.rows.data();
+        sw[s].blk_slots = pl.blk_slots.data();
+        sw[s].blk_bcol = pl.blk_bcol.data();
+    }
+    const pangulu_uint64_t xlen = (pangulu_uint64_t)S.nbk * S.nb;
+    if (plat.block_trsm_multi)
+    {
+        plat.block_trsm_multi((pangulu_inblock_idx)S.nb, &sw[0], &sw[1], X, xlen, (pangulu_uint64_t)npanel, w);
+        return;
+    }
+    for (size_t p = 0; p < npanel; p++)
+        for (int s = 0; s < 2; s++)
+            plat.block_trsv((pangulu_inblock_idx)S.nb, s, sw[s].nlevel, sw[s].level_ptr, sw[s].rows, sw[s].blk_slots, sw[s].blk_bcol, X + p * xlen, xlen);
 }
 
 void triangular_solve(Solver &S, val_t *rhs)
 {
-    if (device_solve(S, rhs))
+    Platform &plat = active_platform();
+    if (device_solve_enabled(S, plat))
+    {
+        // the block solve with one column
+        std::vector<val_t> x((size_t)S.nbk * S.nb, vmake(0));
+        std::copy(rhs, rhs + S.n, x.begin());
+        const int one = 1;
+        device_solve_panels(S, plat, x.data(), 1, &one);
+        std::copy(x.begin(), x.begin() + S.n, rhs);
         return;
+    }
     download_factors(S);
     Comm *comm = world();
     const BlockPattern &P = S.pat;
@@ -224,7 +244,7 @@ void triangular_solve(Solver &S, val_t *rhs)
     std::copy(x.begin(), x.begin() + S.n, rhs);
 }
 
-// Panels of right-hand sides through pangulu_platform_0201001_block_trsm_multi where device_solve() would run, the sweep above
+// Panels of right-hand sides through pangulu_platform_0201001_block_trsm_multi where the device solve runs, triangular_solve()
 // column by column everywhere else (N > 1 ranks, host-memory platforms, PANGULU_AMD_DEVICE_SOLVE=0): collective, same tags.
 void triangular_solve_multi(Solver &S, val_t *Bm, u32 nrhs)
 {
@@ -241,19 +261,6 @@ void triangular_solve_multi(Solver &S, val_t *Bm, u32 nrhs)
     S.last_solve_device_columns = (int)nrhs;
     const u32 nb = S.nb, n = S.n;
     const int wmax = plat.block_trsm_multi((pangulu_inblock_idx)nb, nullptr, nullptr, nullptr, 0, 0, nullptr);
-    if (wmax < 2)
-    {
-        // nb too large for even two columns' tiles in LDS: the single-vector device sweep per column
-        for (u32 j = 0; j < nrhs; j++)
-            triangular_solve(S, Bm + (size_t)j * n);
-        return;
-    }
-    if (!S.solve_plan_ready)
-    {
-        build_sweep_plan(S, true, S.solve_plan[0]);
-        build_sweep_plan(S, false, S.solve_plan[1]);
-        S.solve_plan_ready = true;
-    }
     // panels: the widest width while that many columns are left, then the smallest power of two that holds the rest (zero columns pad it)
     std::vector<int> w;
     size_t total_w = 0;
@@ -288,17 +295,7 @@ void triangular_solve_multi(Solver &S, val_t *Bm, u32 nrhs)
                        for (u32 i = 0; i < n; i++)
                            Xp[(size_t)i * wp + r] = col[i];
                    } });
-    pangulu_hip_solve_sweep_t sw[2];
-    for (int s = 0; s < 2; s++)
-    {
-        const SolveSweepPlan &pl = S.solve_plan[s];
-        sw[s].nlevel = pl.nlevel;
-        sw[s].level_ptr = pl.level_ptr.data();
-        sw[s].rows = pl.rows.data();
-        sw[s].blk_slots = pl.blk_slots.data();
-        sw[s].blk_bcol = pl.blk_bcol.data();
-    }
-    plat.block_trsm_multi((pangulu_inblock_idx)nb, &sw[0], &sw[1], X.data(), (pangulu_uint64_t)xlen, (pangulu_uint64_t)w.size(), w.data());
+    device_solve_panels(S, plat, X.data(), w.size(), w.data());
     each_panel([&](val_t *Xp, int wp, u32 j0, u32 nc)
                {
                    for (u32 r = 0; r < nc; r++)

@@ -1,18 +1,28 @@
-// pg_hip_block_solve_multi.h -- device kernels of the level-scheduled block triangular solve for a PANEL of W right-hand sides
-// (pangulu_amd_gstrs_multi on one rank, pangulu_platform_0201001_block_trsm_multi).  Included inside the anonymous namespace of
-// pg_hip_platform.hip, after pg_hip_block_solve.h (descriptors SolveBlkD / SolveRowD).
+// pg_hip_block_solve_multi.h -- the device kernels of the level-scheduled block triangular solve: a PANEL of W right-hand sides per
+// launch, W = 1 for pangulu_gstrs and up to 16 for pangulu_amd_gstrs_multi (pangulu_platform_0201001_block_trsv and
+// ..._block_trsm_multi launch the same instances).  Included inside the anonymous namespace of pg_hip_platform.hip, after
+// pg_hip_block_solve.h (descriptors SolveBlkD / SolveRowD, the column-by-column kernels of PANGULU_HIP_SOLVE_CHUNKED=0).
 #pragma once
 
 // -----------------------------------------------------------------------------------------------------------------
-// The single-vector sweep (pg_hip_block_solve.h) is an HBM stream of the factor records plus two launches per level; neither
-// depends on how many vectors ride along.  Here every factor entry is read once and applied to W values.
+// Round 4: two launches per level, built around where the column-by-column kernels' time went (fem27(112): 540 launches, 394 ms).
+// That gather kernel walks a block column by column, sixteen lanes a column, every entry a floating-point atomic on the row's
+// 256 words in HBM (hundreds of blocks of a row near the root contend for them): 98 % of its wave cycles waiting.  That level
+// kernel sweeps a diagonal half column by column straight from HBM: nb dependent round trips.
+//  * gather: the block's entries flat over the workgroup (coalesced loads, the column of an entry by bisection in an LDS copy of the
+//    column pointers), products accumulated in LDS (ds_add_f64), ONE global atomic per touched row of the segment at the end;
+//  * level: the diagonal half streams through LDS in chunks of `ch` columns (rows for the upper sweep), double-buffered: three
+//    wavefronts fetch chunk k + 1 while the first one sweeps chunk k out of LDS -- a dependent step costs LDS round trips, not HBM ones.
+//
+// A sweep is an HBM stream of the factor records plus two launches per level; neither depends on how many vectors ride along.
+// Every factor entry is read once and applied to W values.
 //
 // A panel is stored with the right-hand side fastest: X[i * W + r], i = row of the padded system, r = right-hand side.  In LDS
 // a segment is an nb x W tile with a row pitch of W + 1 values (W = 1: no padding): the W lanes of one entry touch W contiguous
 // words and never conflict among themselves; which rows two different entries of a wavefront step touch is data, and with a
 // pitch of W values (a power of two) rows i and i + 32 / (W words) would always share their banks -- the odd pitch spreads them.
 //
-// Same per-block arithmetic as the single-vector kernels: spmv, unit-lower column sweep, upper row sweep with the
+// Same per-block arithmetic as the column-by-column kernels: spmv, unit-lower column sweep, upper row sweep with the
 // PANGULU_SPTRSV_TOL clamp (real part only for complex); sums across blocks arrive in a different order.
 // -----------------------------------------------------------------------------------------------------------------
 __host__ __device__ constexpr int solve_multi_pitch(int w) { return w > 1 ? w + 1 : 1; }
@@ -73,7 +83,7 @@ __global__ __launch_bounds__(256) void block_trsm_gather_multi_kernel(const Solv
 
 // The diagonal halves of the level's block rows: one workgroup per row, the nb x W segment in LDS, the diagonal half streamed
 // through LDS in double-buffered chunks of `ch` columns (rows for the upper sweep) -- three wavefronts fetch chunk k + 1 while
-// the first one sweeps chunk k (block_trsv_level_chunked_kernel's scheme).  A wavefront step is 64 / W entries x W right-hand sides.
+// the first one sweeps chunk k.  A wavefront step is 64 / W entries x W right-hand sides.
 template <bool UPPER, int W>
 __global__ __launch_bounds__(256) void block_trsm_level_multi_kernel(const SolveRowD *__restrict__ rows, int nb, val_t *__restrict__ x, int ch)
 {
@@ -186,6 +196,7 @@ __global__ __launch_bounds__(256) void block_trsm_level_multi_kernel(const Solve
 }
 
 // LDS demand of the two kernels for a panel of w right-hand sides, and the chunk depth the level kernel gets out of `budget` bytes
+// (at most 16 columns; 0: not even one fits beside the segment)
 inline size_t solve_multi_lds_gather(size_t nb, int w)
 {
     return 2 * sizeof(val_t) * nb * (size_t)solve_multi_pitch(w) + sizeof(u32) * (nb + 1) + sizeof(u32) * nb;

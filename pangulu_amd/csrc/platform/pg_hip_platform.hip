@@ -804,41 +804,188 @@ namespace
 
 #include "pg_hip_backend.h"
 
-// device-side descriptors of one sweep (block_trsv's arguments), appended to hr / hb: rows keep their order, the blocks of level l
-// are hb[blk_level_ptr[l] .. blk_level_ptr[l + 1]) counted from the first block appended here
-void append_solve_descriptors(int upper, pangulu_uint64_t nlevel, const pangulu_uint64_t *level_ptr, const pangulu_hip_solve_row_t *rows,
-                              pangulu_storage_slot_t *const *blk_slots, const pangulu_exblock_idx *blk_bcol, std::vector<SolveRowD> &hr,
-                              std::vector<SolveBlkD> &hb, std::vector<size_t> &blk_level_ptr)
+// device-side descriptors of one sweep, appended to hr / hb: rows keep their order, the blocks of level l are
+// hb[blk_level_ptr[l] .. blk_level_ptr[l + 1]) counted from the first block appended here
+void append_solve_descriptors(int upper, const pangulu_hip_solve_sweep_t &sw, std::vector<SolveRowD> &hr, std::vector<SolveBlkD> &hb,
+                              std::vector<size_t> &blk_level_ptr)
 {
     const size_t r0 = hr.size(), b0 = hb.size();
-    hr.resize(r0 + (size_t)level_ptr[nlevel]);
-    blk_level_ptr.assign((size_t)nlevel + 1, 0);
-    for (size_t l = 0; l < (size_t)nlevel; l++)
+    hr.resize(r0 + (size_t)sw.level_ptr[sw.nlevel]);
+    blk_level_ptr.assign((size_t)sw.nlevel + 1, 0);
+    for (size_t l = 0; l < (size_t)sw.nlevel; l++)
     {
-        for (size_t r = (size_t)level_ptr[l]; r < (size_t)level_ptr[l + 1]; r++)
+        for (size_t r = (size_t)sw.level_ptr[l]; r < (size_t)sw.level_ptr[l + 1]; r++)
         {
-            const slot_t *d = rows[r].diag;
+            const pangulu_hip_solve_row_t &row = sw.rows[r];
+            const slot_t *d = row.diag;
             SolveRowD &R = hr[r0 + r];
-            R.brow = rows[r].brow;
-            R.nblk = rows[r].nblk;
+            R.brow = row.brow;
+            R.nblk = row.nblk;
             R.first = hb.size() - b0;
             R.dptr = upper ? d->d_rowpointer : d->d_columnpointer;
             R.didx = upper ? d->d_columnindex : d->d_rowindex;
             R.dval = d->d_value;
-            for (size_t b = 0; b < rows[r].nblk; b++)
+            for (size_t b = 0; b < row.nblk; b++)
             {
-                const slot_t *sb = blk_slots[rows[r].first + b];
+                const slot_t *sb = sw.blk_slots[row.first + b];
                 SolveBlkD D;
                 D.cp = sb->d_columnpointer;
                 D.ri = sb->d_rowindex;
                 D.val = sb->d_value;
-                D.bcol = blk_bcol[rows[r].first + b];
-                D.brow = rows[r].brow;
+                D.bcol = sw.blk_bcol[row.first + b];
+                D.brow = row.brow;
                 hb.push_back(D);
             }
         }
         blk_level_ptr[l + 1] = hb.size() - b0;
     }
+}
+
+// The solve kernels allow themselves 96 KB of LDS.  PANGULU_HIP_SOLVE_CHUNKED=0, or an nb at which not even one chunk column of a
+// diagonal half fits beside the segment, leaves the column-by-column kernels of pg_hip_block_solve.h, which take single vectors.
+constexpr size_t SOLVE_LDS_BUDGET = (size_t)96 << 10;
+bool solve_by_column(size_t nb)
+{
+    static const bool chunked_on = !(getenv("PANGULU_HIP_SOLVE_CHUNKED") && atoi(getenv("PANGULU_HIP_SOLVE_CHUNKED")) == 0);
+    return !chunked_on || solve_multi_chunk(nb, 1, SOLVE_LDS_BUDGET) < 1;
+}
+// the widest panel: a tile row of at most 128 bytes (16 real values, 8 double-complex ones), and both kernels within the budget
+int solve_widest_panel(size_t nb)
+{
+    if (solve_by_column(nb))
+        return 1;
+    int wmax = (int)std::min<size_t>(16, 128 / sizeof(val_t));
+    while (wmax > 1 && (solve_multi_lds_gather(nb, wmax) > SOLVE_LDS_BUDGET || solve_multi_chunk(nb, wmax, SOLVE_LDS_BUDGET) < 1))
+        wmax >>= 1;
+    return wmax;
+}
+
+// what one sweep of a solve call has on the device: its rows and blocks start at row0 / blk0 of the call's descriptor arrays
+struct SolveSweepD
+{
+    int upper;
+    const pangulu_hip_solve_sweep_t *sw;
+    size_t row0, blk0;
+    std::vector<size_t> blk_level_ptr;
+};
+
+// the launches of one panel of W right-hand sides in d_x: the sweeps one after the other, a gather and a level launch per level
+template <int W>
+void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, const SolveRowD *d_rows, const SolveBlkD *d_blks, val_t *d_x)
+{
+    const bool by_column = W == 1 && solve_by_column((size_t)nb);
+    const int ch = by_column ? 0 : solve_multi_chunk((size_t)nb, W, SOLVE_LDS_BUDGET);
+    const size_t lds_gather = solve_multi_lds_gather((size_t)nb, W), lds_level = solve_multi_lds_level((size_t)nb, W, ch);
+    if (!by_column)
+    {
+        static size_t allowed_gather = 0, allowed_level = 0; // (per W: one instantiation per width)
+        if (lds_gather > allowed_gather)
+        {
+            HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_gather_multi_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gather));
+            allowed_gather = lds_gather;
+        }
+        if (lds_level > allowed_level)
+        {
+            HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_multi_kernel<false, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
+            HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_multi_kernel<true, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
+            allowed_level = lds_level;
+        }
+    }
+    for (const SolveSweepD &S : sweeps)
+        for (size_t l = 0; l < (size_t)S.sw->nlevel; l++)
+        {
+            const pangulu_uint64_t *lp = S.sw->level_ptr;
+            const size_t n = (size_t)(lp[l + 1] - lp[l]), nbl = S.blk_level_ptr[l + 1] - S.blk_level_ptr[l];
+            if (!n)
+                continue;
+            const SolveBlkD *blks = d_blks + S.blk0 + S.blk_level_ptr[l];
+            const SolveRowD *rows = d_rows + S.row0 + lp[l];
+            if (by_column)
+            {
+                const size_t lds = sizeof(val_t) * (size_t)nb;
+                if (nbl)
+                    hipLaunchKernelGGL(block_trsv_gather_kernel, dim3((unsigned)nbl), dim3(256), 0, B.stream, blks, nb, d_x);
+                if (S.upper)
+                    hipLaunchKernelGGL(block_trsv_level_kernel<true>, dim3((unsigned)n), dim3(64), lds, B.stream, rows, nb, d_x);
+                else
+                    hipLaunchKernelGGL(block_trsv_level_kernel<false>, dim3((unsigned)n), dim3(64), lds, B.stream, rows, nb, d_x);
+                continue;
+            }
+            if (nbl)
+                hipLaunchKernelGGL(block_trsm_gather_multi_kernel<W>, dim3((unsigned)nbl), dim3(256), lds_gather, B.stream, blks, nb, d_x);
+            if (S.upper)
+                hipLaunchKernelGGL((block_trsm_level_multi_kernel<true, W>), dim3((unsigned)n), dim3(256), lds_level, B.stream, rows, nb, d_x, ch);
+            else
+                hipLaunchKernelGGL((block_trsm_level_multi_kernel<false, W>), dim3((unsigned)n), dim3(256), lds_level, B.stream, rows, nb, d_x, ch);
+        }
+}
+
+// The level-scheduled block triangular solve, both operators' body: the descriptors of the given sweeps (one, or the lower and then
+// the upper one) go up once; the panels of the HOST buffer X (panel p: xlen x w[p] values, right-hand side fastest, w[p] a width
+// solve_widest_panel() allows) then pass through one device buffer one after the other: upload, the sweeps, download.
+void block_solve_panels(int nb, const std::vector<const pangulu_hip_solve_sweep_t *> &sw, const std::vector<int> &upper, val_t *X, size_t xlen, size_t npanel,
+                        const int *w)
+{
+    ensure_ready();
+    std::lock_guard<std::mutex> g(B.mutex);
+    flush_pending_getrf();
+    HIP_CHECK(hipSetDevice(B.device));
+    join_records(B.stream); // the sparse records of finished blocks are written on the records stream
+    join_background(B.stream);
+    std::vector<SolveRowD> hr;
+    std::vector<SolveBlkD> hb;
+    std::vector<SolveSweepD> sweeps(sw.size());
+    for (size_t s = 0; s < sw.size(); s++)
+    {
+        sweeps[s].upper = upper[s];
+        sweeps[s].sw = sw[s];
+        sweeps[s].row0 = hr.size();
+        sweeps[s].blk0 = hb.size();
+        append_solve_descriptors(upper[s], *sw[s], hr, hb, sweeps[s].blk_level_ptr);
+    }
+    if (hr.empty())
+        hr.resize(1);
+    if (hb.empty())
+        hb.resize(1);
+    const int wtop = *std::max_element(w, w + npanel);
+    SolveRowD *d_rows = nullptr;
+    SolveBlkD *d_blks = nullptr;
+    val_t *d_x = nullptr;
+    HIP_CHECK(hipMalloc((void **)&d_rows, sizeof(SolveRowD) * hr.size()));
+    HIP_CHECK(hipMalloc((void **)&d_blks, sizeof(SolveBlkD) * hb.size()));
+    HIP_CHECK(hipMalloc((void **)&d_x, sizeof(val_t) * xlen * (size_t)wtop));
+    HIP_CHECK(hipMemcpyAsync(d_rows, hr.data(), sizeof(SolveRowD) * hr.size(), hipMemcpyHostToDevice, B.stream));
+    HIP_CHECK(hipMemcpyAsync(d_blks, hb.data(), sizeof(SolveBlkD) * hb.size(), hipMemcpyHostToDevice, B.stream));
+    for (size_t p = 0; p < npanel; p++)
+    {
+        const size_t bytes = sizeof(val_t) * xlen * (size_t)w[p];
+        HIP_CHECK(hipMemcpyAsync(d_x, X, bytes, hipMemcpyHostToDevice, B.stream));
+        switch (w[p])
+        {
+        case 1:
+            launch_solve_panel<1>(nb, sweeps, d_rows, d_blks, d_x);
+            break;
+        case 2:
+            launch_solve_panel<2>(nb, sweeps, d_rows, d_blks, d_x);
+            break;
+        case 4:
+            launch_solve_panel<4>(nb, sweeps, d_rows, d_blks, d_x);
+            break;
+        case 8:
+            launch_solve_panel<8>(nb, sweeps, d_rows, d_blks, d_x);
+            break;
+        default:
+            launch_solve_panel<16>(nb, sweeps, d_rows, d_blks, d_x);
+            break;
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(X, d_x, bytes, hipMemcpyDeviceToHost, B.stream));
+        X += xlen * (size_t)w[p];
+    }
+    HIP_CHECK(hipStreamSynchronize(B.stream));
+    HIP_CHECK(hipFree(d_rows));
+    HIP_CHECK(hipFree(d_blks));
+    HIP_CHECK(hipFree(d_x));
 }
 
 const double SV = (double)sizeof(val_t);
@@ -1540,210 +1687,32 @@ extern "C"
         }
     }
 
-    // Level-scheduled block triangular solve (see block_trsv_level_kernel).  `x` is a HOST vector of nbk*nb values: copied
-    // to the device, swept forward (L, unit diagonal) or backward (U), copied back.  rows[level_ptr[l] .. level_ptr[l+1]) are
-    // the block rows of level l; row r's off-diagonal blocks are blk_slots / blk_bcol[rows[r].first .. + rows[r].nblk).
+    // One sweep of the level-scheduled block triangular solve (pg_hip_block_solve_multi.h) for one HOST vector of nbk*nb values: copied
+    // to the device, swept forward (L, unit diagonal) or backward (U), copied back.  rows[level_ptr[l] .. level_ptr[l+1]) are the block
+    // rows of level l; row r's off-diagonal blocks are blk_slots / blk_bcol[rows[r].first .. + rows[r].nblk).
     void pangulu_platform_0201001_block_trsv(pangulu_inblock_idx nb, int upper, pangulu_uint64_t nlevel, const pangulu_uint64_t *level_ptr,
                                              const pangulu_hip_solve_row_t *rows, pangulu_storage_slot_t *const *blk_slots,
                                              const pangulu_exblock_idx *blk_bcol, calculate_type *x, pangulu_uint64_t xlen)
     {
-        ensure_ready();
-        std::lock_guard<std::mutex> g(B.mutex);
-        flush_pending_getrf();
-        HIP_CHECK(hipSetDevice(B.device));
-        join_records(B.stream); // the sparse records of finished blocks are written on the records stream
-        join_background(B.stream);
-        std::vector<SolveRowD> hr;
-        std::vector<SolveBlkD> hb;
-        std::vector<size_t> blk_level_ptr;
-        append_solve_descriptors(upper, nlevel, level_ptr, rows, blk_slots, blk_bcol, hr, hb, blk_level_ptr);
-        if (hr.empty())
-            hr.resize(1);
-        if (hb.empty())
-            hb.resize(1);
-        SolveRowD *d_rows = nullptr;
-        SolveBlkD *d_blks = nullptr;
-        val_t *d_x = nullptr;
-        HIP_CHECK(hipMalloc((void **)&d_rows, sizeof(SolveRowD) * hr.size()));
-        HIP_CHECK(hipMalloc((void **)&d_blks, sizeof(SolveBlkD) * hb.size()));
-        HIP_CHECK(hipMalloc((void **)&d_x, sizeof(val_t) * (size_t)xlen));
-        HIP_CHECK(hipMemcpyAsync(d_rows, hr.data(), sizeof(SolveRowD) * hr.size(), hipMemcpyHostToDevice, B.stream));
-        HIP_CHECK(hipMemcpyAsync(d_blks, hb.data(), sizeof(SolveBlkD) * hb.size(), hipMemcpyHostToDevice, B.stream));
-        HIP_CHECK(hipMemcpyAsync(d_x, x, sizeof(val_t) * (size_t)xlen, hipMemcpyHostToDevice, B.stream));
-        const size_t lds = sizeof(val_t) * (size_t)nb;
-        // round 4 kernels (PANGULU_HIP_SOLVE_CHUNKED=0: the column-by-column ones): chunks of `ch` columns of a diagonal half
-        // through at most 96 KB of LDS
-        static const bool chunked_on = !(getenv("PANGULU_HIP_SOLVE_CHUNKED") && atoi(getenv("PANGULU_HIP_SOLVE_CHUNKED")) == 0);
-        const size_t per_col = 2 * (size_t)nb * (sizeof(val_t) + sizeof(u16)); // both buffers
-        int ch = (int)std::min<size_t>(16, ((size_t)96 << 10) / per_col);
-        ch = std::min(ch, (int)nb);
-        const bool chunked = chunked_on && ch >= 1;
-        const size_t lds_level = sizeof(val_t) * (size_t)nb + 2 * (size_t)ch * nb * (sizeof(val_t) + sizeof(u16)) + sizeof(u32) * ((size_t)nb + 2) + 16;
-        const size_t lds_gather = 2 * sizeof(val_t) * (size_t)nb + sizeof(u32) * ((size_t)nb + 1);
-        if (chunked)
-        {
-            static size_t allowed = 0;
-            if (lds_level > allowed)
-            {
-                HIP_CHECK(hipFuncSetAttribute((const void *)block_trsv_level_chunked_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
-                HIP_CHECK(hipFuncSetAttribute((const void *)block_trsv_level_chunked_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
-                HIP_CHECK(hipFuncSetAttribute((const void *)block_trsv_gather_flat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(lds_gather, (size_t)1)));
-                allowed = lds_level;
-            }
-        }
-        for (size_t l = 0; l < (size_t)nlevel; l++)
-        {
-            const size_t n = (size_t)(level_ptr[l + 1] - level_ptr[l]), nbl = blk_level_ptr[l + 1] - blk_level_ptr[l];
-            if (!n)
-                continue;
-            if (chunked)
-            {
-                if (nbl)
-                    hipLaunchKernelGGL(block_trsv_gather_flat_kernel, dim3((unsigned)nbl), dim3(256), lds_gather, B.stream, d_blks + blk_level_ptr[l], (int)nb, d_x);
-                if (upper)
-                    hipLaunchKernelGGL(block_trsv_level_chunked_kernel<true>, dim3((unsigned)n), dim3(256), lds_level, B.stream, d_rows + level_ptr[l], (int)nb, d_x, ch);
-                else
-                    hipLaunchKernelGGL(block_trsv_level_chunked_kernel<false>, dim3((unsigned)n), dim3(256), lds_level, B.stream, d_rows + level_ptr[l], (int)nb, d_x, ch);
-                continue;
-            }
-            if (nbl)
-                hipLaunchKernelGGL(block_trsv_gather_kernel, dim3((unsigned)nbl), dim3(256), 0, B.stream, d_blks + blk_level_ptr[l], (int)nb, d_x);
-            if (upper)
-                hipLaunchKernelGGL(block_trsv_level_kernel<true>, dim3((unsigned)n), dim3(64), lds, B.stream, d_rows + level_ptr[l], (int)nb, d_x);
-            else
-                hipLaunchKernelGGL(block_trsv_level_kernel<false>, dim3((unsigned)n), dim3(64), lds, B.stream, d_rows + level_ptr[l], (int)nb, d_x);
-        }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(x, d_x, sizeof(val_t) * (size_t)xlen, hipMemcpyDeviceToHost, B.stream));
-        HIP_CHECK(hipStreamSynchronize(B.stream));
-        HIP_CHECK(hipFree(d_rows));
-        HIP_CHECK(hipFree(d_blks));
-        HIP_CHECK(hipFree(d_x));
+        const pangulu_hip_solve_sweep_t sw = {nlevel, level_ptr, rows, blk_slots, blk_bcol};
+        const int one = 1;
+        block_solve_panels((int)nb, {&sw}, {upper ? 1 : 0}, x, (size_t)xlen, 1, &one);
     }
 
-    // Both sweeps for panels of right-hand sides (see pg_hip_block_solve_multi.h).  The descriptors of both sweeps go up once; the
-    // panels then pass through one device buffer one after the other: upload, L sweep, U sweep, download.
+    // Both sweeps for panels of right-hand sides: the descriptors of both sweeps go up once and serve all the panels.
     int pangulu_platform_0201001_block_trsm_multi(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *lower, const pangulu_hip_solve_sweep_t *upper,
                                                   calculate_type *X, pangulu_uint64_t xlen, pangulu_uint64_t npanel, const int *w)
     {
-        // the widest panel: a tile row of at most 128 bytes (16 real values, 8 double-complex ones), and both kernels within the
-        // 96 KB of LDS the single-vector solve kernels allow themselves
-        const size_t budget = (size_t)96 << 10;
-        int wmax = (int)std::min<size_t>(16, 128 / sizeof(val_t));
-        while (wmax > 1 && (solve_multi_lds_gather(nb, wmax) > budget || solve_multi_chunk(nb, wmax, budget) < 1))
-            wmax >>= 1;
+        const int wmax = solve_widest_panel(nb);
         if (npanel == 0)
             return wmax;
-        int wtop = 1;
         for (size_t p = 0; p < (size_t)npanel; p++)
-        {
             if (w[p] < 1 || w[p] > wmax || (w[p] & (w[p] - 1)))
             {
                 fprintf(stderr, "[PanguLU-AMD ERROR] block_trsm_multi: panel width %d (nb = %d takes powers of two up to %d)\n", w[p], (int)nb, wmax);
                 exit(EXIT_FAILURE);
             }
-            wtop = std::max(wtop, w[p]);
-        }
-        if (solve_multi_lds_gather(nb, 1) > budget || solve_multi_chunk(nb, 1, budget) < 1)
-        {
-            fprintf(stderr, "[PanguLU-AMD ERROR] block_trsm_multi: nb = %d does not fit the solve kernels' LDS\n", (int)nb);
-            exit(EXIT_FAILURE);
-        }
-        ensure_ready();
-        std::lock_guard<std::mutex> g(B.mutex);
-        flush_pending_getrf();
-        HIP_CHECK(hipSetDevice(B.device));
-        join_records(B.stream); // the sparse records of finished blocks are written on the records stream
-        join_background(B.stream);
-        const pangulu_hip_solve_sweep_t *sweep[2] = {lower, upper};
-        std::vector<SolveRowD> hr;
-        std::vector<SolveBlkD> hb;
-        std::vector<size_t> blk_level_ptr[2];
-        size_t row0[2], blk0[2];
-        for (int s = 0; s < 2; s++)
-        {
-            row0[s] = hr.size();
-            blk0[s] = hb.size();
-            append_solve_descriptors(s, sweep[s]->nlevel, sweep[s]->level_ptr, sweep[s]->rows, sweep[s]->blk_slots, sweep[s]->blk_bcol, hr, hb, blk_level_ptr[s]);
-        }
-        if (hr.empty())
-            hr.resize(1);
-        if (hb.empty())
-            hb.resize(1);
-        SolveRowD *d_rows = nullptr;
-        SolveBlkD *d_blks = nullptr;
-        val_t *d_x = nullptr;
-        HIP_CHECK(hipMalloc((void **)&d_rows, sizeof(SolveRowD) * hr.size()));
-        HIP_CHECK(hipMalloc((void **)&d_blks, sizeof(SolveBlkD) * hb.size()));
-        HIP_CHECK(hipMalloc((void **)&d_x, sizeof(val_t) * (size_t)xlen * (size_t)wtop));
-        HIP_CHECK(hipMemcpyAsync(d_rows, hr.data(), sizeof(SolveRowD) * hr.size(), hipMemcpyHostToDevice, B.stream));
-        HIP_CHECK(hipMemcpyAsync(d_blks, hb.data(), sizeof(SolveBlkD) * hb.size(), hipMemcpyHostToDevice, B.stream));
-        auto run_panel = [&](auto wc)
-        {
-            constexpr int W = decltype(wc)::value;
-            const int ch = solve_multi_chunk(nb, W, budget);
-            const size_t lds_gather = solve_multi_lds_gather(nb, W), lds_level = solve_multi_lds_level(nb, W, ch);
-            static size_t allowed_gather = 0, allowed_level = 0; // (per W: the lambda is instantiated once per width)
-            if (lds_gather > allowed_gather)
-            {
-                HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_gather_multi_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gather));
-                allowed_gather = lds_gather;
-            }
-            if (lds_level > allowed_level)
-            {
-                HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_multi_kernel<false, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
-                HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_multi_kernel<true, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
-                allowed_level = lds_level;
-            }
-            for (int s = 0; s < 2; s++)
-                for (size_t l = 0; l < (size_t)sweep[s]->nlevel; l++)
-                {
-                    const pangulu_uint64_t *lp = sweep[s]->level_ptr;
-                    const size_t n = (size_t)(lp[l + 1] - lp[l]), nbl = blk_level_ptr[s][l + 1] - blk_level_ptr[s][l];
-                    if (!n)
-                        continue;
-                    if (nbl)
-                        hipLaunchKernelGGL(block_trsm_gather_multi_kernel<W>, dim3((unsigned)nbl), dim3(256), lds_gather, B.stream,
-                                           d_blks + blk0[s] + blk_level_ptr[s][l], (int)nb, d_x);
-                    if (s)
-                        hipLaunchKernelGGL((block_trsm_level_multi_kernel<true, W>), dim3((unsigned)n), dim3(256), lds_level, B.stream,
-                                           d_rows + row0[s] + lp[l], (int)nb, d_x, ch);
-                    else
-                        hipLaunchKernelGGL((block_trsm_level_multi_kernel<false, W>), dim3((unsigned)n), dim3(256), lds_level, B.stream,
-                                           d_rows + row0[s] + lp[l], (int)nb, d_x, ch);
-                }
-        };
-        val_t *Xp = X;
-        for (size_t p = 0; p < (size_t)npanel; p++)
-        {
-            const size_t bytes = sizeof(val_t) * (size_t)xlen * (size_t)w[p];
-            HIP_CHECK(hipMemcpyAsync(d_x, Xp, bytes, hipMemcpyHostToDevice, B.stream));
-            switch (w[p])
-            {
-            case 1:
-                run_panel(std::integral_constant<int, 1>());
-                break;
-            case 2:
-                run_panel(std::integral_constant<int, 2>());
-                break;
-            case 4:
-                run_panel(std::integral_constant<int, 4>());
-                break;
-            case 8:
-                run_panel(std::integral_constant<int, 8>());
-                break;
-            default:
-                run_panel(std::integral_constant<int, 16>());
-                break;
-            }
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(Xp, d_x, bytes, hipMemcpyDeviceToHost, B.stream));
-            Xp += (size_t)xlen * (size_t)w[p];
-        }
-        HIP_CHECK(hipStreamSynchronize(B.stream));
-        HIP_CHECK(hipFree(d_rows));
-        HIP_CHECK(hipFree(d_blks));
-        HIP_CHECK(hipFree(d_x));
+        block_solve_panels((int)nb, {lower, upper}, {0, 1}, X, (size_t)xlen, (size_t)npanel, w);
         return wmax;
     }
 

@@ -218,10 +218,12 @@ class BlockMatrix:
             b.free()
 
 
-def exported_records(mat, nb, vtype="r64", ordering="nd", user_perm=None):
+def exported_records(mat, nb, vtype="r64", ordering="nd", user_perm=None, factorise=False):
     """Block records (patterns closed under fill, values = A on its pattern, 0 on fill) as the host builds them.
     `user_perm` (perm[new] = old): the permutation to use instead of computing an ordering -- a fixture that carries its
-    permutation pins the operators, not the ordering code."""
+    permutation pins the operators, not the ordering code.
+    `factorise`: the records after pangulu_gstrf -- the factors -- and the handle's permutation (perm[new] = old, n_padded
+    entries, padding rows >= n), as (records, perm)."""
     import pangulu_amd as pa
 
     from .helpers import library_for, oracle_library
@@ -232,6 +234,9 @@ def exported_records(mat, nb, vtype="r64", ordering="nd", user_perm=None):
         h = pa.pangulu_init(n, len(va), cp, ri, va, nb=nb, vtype=vtype, ordering="user", user_perm=user_perm, lib=lib)
     else:
         h = pa.pangulu_init(n, len(va), cp, ri, va, nb=nb, vtype=vtype, ordering=ordering, coords=coords if ordering == "nd" else None, lib=lib)
+    if factorise:
+        pa.pangulu_gstrf(h)
     recs = list(pa.owned_blocks(h))
+    perm = pa.permutation(h)
     pa.pangulu_finalize(h)
-    return recs
+    return (recs, perm) if factorise else recs

@@ -4,6 +4,8 @@
 // block-sparse L (unit) and U are swept level by level, gather launch then level launch, like pangulu_platform_0201001_block_trsm_multi
 // does.  The result is compared with dense substitution per right-hand side.  It checks the kernels' indexing and arithmetic for every
 // panel width, block orders that are no multiple of anything and several chunks per diagonal half; it says nothing about the device.
+// W = 1 is what pangulu_gstrs launches (pangulu_platform_0201001_block_trsv and a width-1 panel of block_trsm_multi alike): the
+// default single-vector kernels are tested here too.
 #include <algorithm>
 #include <atomic>
 #include <barrier>

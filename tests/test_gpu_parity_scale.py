@@ -165,7 +165,7 @@ def test_other_value_types_nb128(vtype, gen, nb):
 ], ids=["r64_shell40", "r64_kkt8", "cr64_poisson12", "r32_fem27_10"])
 def test_device_solve_matches_host_sweep(vtype, gen, nb, monkeypatch):
     """pangulu_gstrs on one rank runs both sweeps on the device-resident factors, level by level
-    (pangulu_platform_0201001_block_trsv); the reference-style host sweep (src/pangulu_sptrsv.c:24-191) on downloaded
+    (pangulu_platform_0201001_block_trsm_multi, one panel of width 1); the reference-style host sweep (src/pangulu_sptrsv.c:24-191) on downloaded
     factors must give the same solution to rounding, and both the oracle's."""
     dt = _lib.VALUE_TYPES[vtype][0]
     mat = gen(dt)

@@ -1,6 +1,13 @@
 """pangulu_amd_gstrs_multi on the device: panels of right-hand sides through pangulu_platform_0201001_block_trsm_multi
 (pg_hip_block_solve_multi.h).  Column j of the block solve must be what pangulu_gstrs gives for that column alone -- the oracle
-library's and the HIP path's own -- within the bounds of test_device_solve_matches_host_sweep."""
+library's and the HIP path's own -- within the bounds of test_device_solve_matches_host_sweep.  pangulu_gstrs on the HIP path is
+the same solve with one panel of width 1 (same kernels, same launch routine, same cached plans): the tests at the end hold it
+across a refactorisation, call the two back-end operators directly, and send width-1 panels through the column-by-column kernels."""
+import ctypes
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -8,7 +15,8 @@ import pangulu_amd as pa
 from pangulu_amd import _lib
 from pangulu_amd import matrices as M
 
-from .solve_multi_common import assert_columns_match, open_handle, oracle_columns, raw_gstrs_multi, rhs_block, solve_columns
+from . import slots
+from .solve_multi_common import TOL, assert_columns_match, open_handle, oracle_columns, raw_gstrs_multi, rhs_block, solve_columns
 
 pytestmark = pytest.mark.gpu
 
@@ -154,3 +162,120 @@ def test_return_codes():
         assert (buf == B).all()
     finally:
         pa.pangulu_finalize(h)
+
+
+@pytest.mark.parametrize("name", ["r64_kkt8", "cr64_poisson12"])
+def test_single_vector_solves_across_a_refactorisation(name, monkeypatch):
+    """pangulu_gstrs sweeps on the plans cached on the handle: after update_values + gstrf they must give the NEW matrix's solution
+    (a stale plan or stale descriptor pointers would show here first)"""
+    monkeypatch.setenv("PANGULU_AMD_DEVICE_SOLVE", "1")
+    mat, nb, vtype, B, ref = case(name)
+    n, cp, ri, va, coords = mat
+    va2 = va * (1.0 + 0.05 * np.cos(np.arange(len(va))))  # same pattern, every entry moved by up to 5 %
+    ref2 = oracle_columns(name + "_new_values", (n, cp, ri, va2, coords), nb, vtype, B)
+    B, ref, ref2 = B[:, :4], ref[:, :4], ref2[:, :4]
+    h = open_handle(mat, nb, "hip", vtype)
+    try:
+        X1 = solve_columns(h, B)
+        pa.update_values(h, va2)
+        pa.pangulu_gstrf(h)
+        X2 = solve_columns(h, B)
+    finally:
+        pa.pangulu_finalize(h)
+    assert_columns_match(X1, ref, B, vtype, "first factorisation")
+    assert_columns_match(X2, ref2, B, vtype, "after update_values")
+    assert np.abs(X2[:, 0] - X1[:, 0]).max() > 1e-3 * np.abs(X1[:, 0]).max()  # (the two systems do differ)
+
+
+class _SolveRow(ctypes.Structure):  # pangulu_hip_solve_row_t
+    _fields_ = [("brow", ctypes.c_uint32), ("nblk", ctypes.c_uint32), ("first", ctypes.c_uint64), ("diag", ctypes.POINTER(slots.Slot))]
+
+
+class _SolveSweep(ctypes.Structure):  # pangulu_hip_solve_sweep_t
+    _fields_ = [("nlevel", ctypes.c_uint64), ("level_ptr", ctypes.POINTER(ctypes.c_uint64)), ("rows", ctypes.POINTER(_SolveRow)),
+                ("blk_slots", ctypes.POINTER(ctypes.POINTER(slots.Slot))), ("blk_bcol", ctypes.POINTER(ctypes.c_uint32))]
+
+
+def _level_plan(bm, lower):
+    """One sweep as the operators take it: block rows grouped by level (1 + the highest level among the rows a row's off-diagonal
+    blocks on the sweep's side read), each with its diagonal half and those blocks."""
+    nbk = bm.nblk
+    side = {r: sorted(c for (br, c, _) in bm.blocks if br == r and (c < r if lower else c > r)) for r in range(nbk)}
+    level = [0] * nbk
+    for r in (range(nbk) if lower else reversed(range(nbk))):
+        level[r] = 1 + max((level[c] for c in side[r]), default=-1)
+    nlevel = 1 + max(level)
+    order = sorted(range(nbk), key=lambda r: (level[r], r))
+    level_ptr = (ctypes.c_uint64 * (nlevel + 1))(*np.concatenate(([0], np.cumsum(np.bincount(level, minlength=nlevel)))).tolist())
+    nblk = sum(len(v) for v in side.values())
+    rows = (_SolveRow * nbk)()
+    blk_slots = (ctypes.POINTER(slots.Slot) * max(nblk, 1))()
+    blk_bcol = (ctypes.c_uint32 * max(nblk, 1))()
+    k = 0
+    for i, r in enumerate(order):
+        rows[i].brow, rows[i].nblk, rows[i].first = r, len(side[r]), k
+        rows[i].diag = ctypes.pointer(bm.blocks[(r, r, 0 if lower else 1)].slot)
+        for c in side[r]:
+            blk_slots[k] = ctypes.pointer(bm.get(r, c).slot)
+            blk_bcol[k] = c
+            k += 1
+    return _SolveSweep(nlevel, level_ptr, rows, blk_slots, blk_bcol)
+
+
+def test_backend_operators_called_directly():
+    """block_trsv (one sweep, one host vector: the native host no longer calls it) lower then upper, and block_trsm_multi with one
+    panel of width 1 on the same plans, on hand-built slots of the oracle's factor records: both give the oracle's pangulu_gstrs
+    solution of the same right-hand side in the factors' ordering.  Not compared bitwise: several blocks add into one row with
+    floating-point atomics, in an order that varies."""
+    mat, nb, vtype, B, ref = case("r64_kkt8")
+    n = mat[0]
+    hip = _lib.load(vtype)
+    hip.pangulu_amd_use_builtin_platform()
+    slots.declare_platform(hip, "0201001")
+    hip.pangulu_platform_0201001_set_default_device(0)
+    recs, perm = slots.exported_records(mat, nb, vtype, factorise=True)
+    bm = slots.BlockMatrix(recs, nb, np.float64, hip)
+    try:
+        xlen = bm.nblk * nb
+        real = perm < n  # (the others are padding rows: 1 * x = 0)
+        b = np.zeros(xlen)
+        want = np.zeros(xlen)
+        b[:len(perm)][real] = B[perm[real], 3]  # the seeded random column
+        want[:len(perm)][real] = ref[perm[real], 3]
+        sw = [_level_plan(bm, True), _level_plan(bm, False)]
+        vp = ctypes.c_void_p
+        trsv, multi = hip.pangulu_platform_0201001_block_trsv, hip.pangulu_platform_0201001_block_trsm_multi
+        trsv.restype = None
+        trsv.argtypes = [ctypes.c_uint16, ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_SolveRow),
+                         ctypes.POINTER(ctypes.POINTER(slots.Slot)), ctypes.POINTER(ctypes.c_uint32), vp, ctypes.c_uint64]
+        multi.restype = ctypes.c_int
+        multi.argtypes = [ctypes.c_uint16, ctypes.POINTER(_SolveSweep), ctypes.POINTER(_SolveSweep), vp, ctypes.c_uint64, ctypes.c_uint64,
+                          ctypes.POINTER(ctypes.c_int)]
+        x1 = b.copy()
+        for upper, s in enumerate(sw):
+            trsv(nb, upper, s.nlevel, s.level_ptr, s.rows, s.blk_slots, s.blk_bcol, x1.ctypes.data_as(vp), xlen)
+        x2 = b.copy()
+        assert multi(nb, None, None, None, 0, 0, None) == 16  # (npanel = 0 only asks)
+        assert multi(nb, ctypes.byref(sw[0]), ctypes.byref(sw[1]), x2.ctypes.data_as(vp), xlen, 1, (ctypes.c_int * 1)(1)) == 16
+    finally:
+        bm.free()
+    scale = np.abs(want).max()
+    for what, x in (("block_trsv, lower then upper", x1), ("block_trsm_multi, one panel of width 1", x2)):
+        err = np.abs(x - want).max()
+        assert err <= TOL[vtype] * scale, "%s: differs from the oracle by %g (scale %g)" % (what, err, scale)
+
+
+def test_width_one_panels_through_the_column_by_column_kernels(tmp_path):
+    """PANGULU_HIP_SOLVE_CHUNKED=0 leaves the kernels that take single vectors: the back-end offers panels of width 1 only, and the
+    block solve sends its columns through them one panel each, in one call (a process of its own: the switch is read once)"""
+    mat, nb, vtype, B, ref = case("r64_kkt8")
+    out = str(tmp_path / "out.npz")
+    env = dict(os.environ, PANGULU_HIP_SOLVE_CHUNKED="0", PANGULU_AMD_DEVICE_SOLVE="1")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    run = subprocess.run([sys.executable, os.path.join(root, "tests", "solve_by_column_worker.py"), "r64_kkt8", "3", out], env=env, cwd=root,
+                         capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    z = np.load(out)
+    assert {k: int(z[k]) for k in ("device_columns", "panel_width", "panels")} == {"device_columns": 3, "panel_width": 1, "panels": 3}
+    assert_columns_match(z["X"], ref[:, :3], B[:, :3], vtype, "column-by-column kernels against the oracle")

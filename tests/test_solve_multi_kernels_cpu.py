@@ -1,6 +1,8 @@
 """The kernels of pg_hip_block_solve_multi.h, compiled as host C++ behind shims for the few device intrinsics they use and run
 with one thread per work-item (tests/solve_multi_kernel_emulation.cpp), against dense substitution: every panel width, both sweeps,
-real and complex values.  A check of indexing and arithmetic that needs no device."""
+real and complex values.  A check of indexing and arithmetic that needs no device.  The W = 1 instances are the kernels every
+pangulu_gstrs on the HIP path launches (a single vector is a panel of width 1), so this is the device-free test of the default
+single-vector solve as well."""
 import os
 import subprocess
 
