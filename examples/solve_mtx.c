@@ -2,13 +2,15 @@
  * solve_mtx.c -- a user program against include/pangulu.h, the way a program written for the reference is
  * (the reference ships examples/example.c:282-300: init, gstrf, gstrs, finalize, then ||Ax - b|| / ||b||).
  *
- *   solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt]
+ *   solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt] [-t]
  *
  * Reads a Matrix Market coordinate file (real / integer / pattern, general / symmetric / skew-symmetric) or -- by the last letter of
  * the name, as the reference's example chooses (examples/example.c:100-163) -- its binary .lid layout (u32 rows, u32 columns, u64
  * entries, then the CSR arrays: u64 row pointers, u32 column indices, values), solves A x = b on the GPU of this process and prints
  * the relative residual.  Without -r the right-hand side is b = A * 1 (the reference's choice,
  * examples/example.c:245-266); with it, a text file holding the length on the first non-comment line and one value per line.
+ * With -t it then solves the transposed system A^T x = b with the same right-hand side on the same factors
+ * (pangulu_amd_gstrs_trans: no second factorisation) and prints || A^T x - b || / || b || as well.
  *
  * One process per GPU: started under a launcher that exports RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT (torch.distributed.run does)
  * every process calls pangulu_amd_comm_init() first -- the place of MPI_Init_thread in the reference's example -- and only rank 0
@@ -191,6 +193,17 @@ static void multiply(const csc_t *A, const sparse_value_t *x, sparse_value_t *y)
             y[A->rowidx[p]] += A->value[p] * x[c];
 }
 
+static void multiply_transposed(const csc_t *A, const sparse_value_t *x, sparse_value_t *y)
+{
+    for (sparse_index_t c = 0; c < A->n; c++)
+    {
+        sparse_value_t acc = 0;
+        for (sparse_pointer_t p = A->colptr[c]; p < A->colptr[c + 1]; p++)
+            acc += A->value[p] * x[A->rowidx[p]];
+        y[c] = acc;
+    }
+}
+
 static void read_vector(const char *path, sparse_index_t n, sparse_value_t *b)
 {
     FILE *f = fopen(path, "r");
@@ -218,18 +231,20 @@ static void read_vector(const char *path, sparse_index_t n, sparse_value_t *b)
 int main(int argc, char **argv)
 {
     const char *mtx = NULL, *rhs = NULL;
-    int nb = 256;
+    int nb = 256, transposed = 0;
     for (int a = 1; a < argc; a++)
-        if (!strcmp(argv[a], "-f") && a + 1 < argc)
+        if (!strcmp(argv[a], "-t"))
+            transposed = 1;
+        else if (!strcmp(argv[a], "-f") && a + 1 < argc)
             mtx = argv[++a];
         else if (!strcmp(argv[a], "-r") && a + 1 < argc)
             rhs = argv[++a];
         else if ((!strcmp(argv[a], "-n") || !strcmp(argv[a], "-nb")) && a + 1 < argc)
             nb = atoi(argv[++a]);
         else
-            die("usage: solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt]", NULL);
+            die("usage: solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt] [-t]", NULL);
     if (!mtx || nb <= 0)
-        die("usage: solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt]", NULL);
+        die("usage: solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt] [-t]", NULL);
 
     const int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0;
     const int size = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
@@ -297,6 +312,28 @@ int main(int argc, char **argv)
                (double)info.flop / (t2 - t1) / 1e9, t3 - t2, size);
         printf("|| Ax - b || / || b || = %le\n", sqrt(rr) / sqrt(bb));
         free(ax);
+    }
+    if (transposed)
+    {
+        /* the same right-hand side, the transposed system, the same factors (collective like pangulu_gstrs) */
+        if (rank == 0)
+            memcpy(x, b, sizeof *x * A.n);
+        double t4 = now_s();
+        int rc = pangulu_amd_gstrs_trans(x, 1, A.n, PANGULU_AMD_TRANS_T, &gstrs_options, &handle);
+        double t5 = now_s();
+        if (rc != 0)
+            die("pangulu_amd_gstrs_trans failed", NULL);
+        if (rank == 0)
+        {
+            sparse_value_t *atx = malloc(sizeof *atx * A.n);
+            multiply_transposed(&A, x, atx);
+            double rr = 0.0, bb = 0.0;
+            for (sparse_index_t i = 0; i < A.n; i++)
+                rr += (atx[i] - b[i]) * (atx[i] - b[i]), bb += b[i] * b[i];
+            printf("transposed solve %.3f s\n", t5 - t4);
+            printf("|| A^T x - b || / || b || = %le\n", sqrt(rr) / sqrt(bb));
+            free(atx);
+        }
     }
     pangulu_finalize(&handle);
     if (size > 1)

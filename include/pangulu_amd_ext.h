@@ -156,7 +156,21 @@ extern "C"
      * Returns 0 (nrhs == 0: nothing to do); 1 if the handle has not been factorised; 2 if ldb < n or rhs == NULL on rank 0. */
     int pangulu_amd_gstrs_multi(sparse_value_t *rhs, sparse_index_t nrhs, sparse_pointer_t ldb, pangulu_gstrs_options *gstrs_options,
                                 void **pangulu_handle);
-    /* what the last pangulu_amd_gstrs_multi on this handle did: columns swept on the device (0: host sweep), panel width used
+    /* Solves A^T X = B (trans = PANGULU_AMD_TRANS_T) or A^H X = B (PANGULU_AMD_TRANS_H; real value types: the same as _T) with the
+     * factors of the last pangulu_gstrf -- no second factorisation of the transpose: A^T = U^T L^T, a forward sweep with U^T and a
+     * backward sweep with L^T over the same block records.  Arguments, layout, collectiveness (rank 0's rhs, nrhs, ldb and trans
+     * decide), info.time_solve and the return codes 0 / 1 / 2 are those of pangulu_amd_gstrs_multi; 3: unknown `trans` on rank 0
+     * (rhs is left untouched).  PANGULU_AMD_TRANS_NONE is pangulu_amd_gstrs_multi itself.  Permutation and padding rows are
+     * handled as there; on a pangulu_amd_set_scaling(1) handle the scalings swap roles (the column scaling and the matching go
+     * onto b, the row scaling onto x).  On one rank with the factors on the device the columns are swept in panels of up to 16
+     * by kernels of their own; otherwise -- several ranks, PANGULU_AMD_DEVICE_SOLVE=0, PANGULU_HIP_SOLVE_CHUNKED=0, a platform
+     * without the operator -- a host sweep over block columns runs once per column. */
+#define PANGULU_AMD_TRANS_NONE 0 /* A   X = B */
+#define PANGULU_AMD_TRANS_T 1    /* A^T X = B */
+#define PANGULU_AMD_TRANS_H 2    /* A^H X = B (real value types: the same as _T) */
+    int pangulu_amd_gstrs_trans(sparse_value_t *rhs, sparse_index_t nrhs, sparse_pointer_t ldb, int trans, pangulu_gstrs_options *gstrs_options,
+                                void **pangulu_handle);
+    /* what the last pangulu_amd_gstrs_multi / pangulu_amd_gstrs_trans on this handle did: columns swept on the device (0: host sweep), panel width used
      * (the widest panel; 1: column by column), number of panels.  Any pointer may be NULL.  Returns 0. */
     int pangulu_amd_last_solve_path(void **pangulu_handle, int *device_columns, int *panel_width, int *panels);
 

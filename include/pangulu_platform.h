@@ -327,6 +327,17 @@ extern "C"
     } pangulu_hip_solve_sweep_t;
     int pangulu_platform_0201001_block_trsm_multi(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *lower, const pangulu_hip_solve_sweep_t *upper,
                                                   calculate_type *X, pangulu_uint64_t xlen, pangulu_uint64_t npanel, const int *w);
+    /* Optional: the TRANSPOSED solve on the same records, A^T X = B (conjugate = 0) or A^H X = B (conjugate != 0; real value types:
+     * the same as A^T): A^T = U^T L^T, so a forward sweep with U^T and then a backward sweep with L^T.  Same contract as
+     * block_trsm_multi -- host panels, right-hand side fastest, the widest panel returned, npanel = 0 only asks -- with the sweeps
+     * described the other way round: a row of `forward_ut` is a DESTINATION segment i (brow) with the UPPER diagonal half as `diag`
+     * and the blocks A(k, i), k < i, of block COLUMN i of U, blk_bcol = k their source segments; `backward_lt` has the LOWER
+     * diagonal half and the blocks A(k, i), k > i, of block column i of L; levels follow those dependencies.  Returns 0 where the
+     * transposed kernels are not available (PANGULU_HIP_SOLVE_CHUNKED=0, or an nb at which no chunk of a diagonal half fits in
+     * LDS: the column-by-column kernels have no transposed twin); nothing is touched then and the caller sweeps on the host. */
+    int pangulu_platform_0201001_block_trsm_multi_trans(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *forward_ut,
+                                                        const pangulu_hip_solve_sweep_t *backward_lt, int conjugate, calculate_type *X,
+                                                        pangulu_uint64_t xlen, pangulu_uint64_t npanel, const int *w);
     /* Optional: y[dst segment] += A_blk * x[src segment] for a list of device-resident block records, in one launch (one
      * workgroup per block, floating-point atomics on y).  `x` and `y` are HOST vectors of `xlen` values (nb per block
      * row / column); y is read, updated and written back.  csr[i] != 0: the record is an upper diagonal half (CSR, diagonal

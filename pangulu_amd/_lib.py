@@ -166,6 +166,8 @@ def load(vtype="r64", test_hooks=False):
     lib.pangulu_gstrs.restype = None
     lib.pangulu_amd_gstrs_multi.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(GstrsOptions), vpp]
     lib.pangulu_amd_gstrs_multi.restype = ctypes.c_int
+    lib.pangulu_amd_gstrs_trans.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(GstrsOptions), vpp]
+    lib.pangulu_amd_gstrs_trans.restype = ctypes.c_int
     lib.pangulu_amd_last_solve_path.argtypes = [vpp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.pangulu_amd_last_solve_path.restype = ctypes.c_int
     lib.pangulu_gssv.argtypes = [vp, ctypes.POINTER(GstrfOptions), ctypes.POINTER(GstrsOptions), vpp]

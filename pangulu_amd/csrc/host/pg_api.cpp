@@ -80,6 +80,7 @@ void bind_builtin_hip(Platform &p)
     p.marker_wait = pangulu_platform_0201001_marker_wait;
     p.block_trsv = pangulu_platform_0201001_block_trsv;
     p.block_trsm_multi = pangulu_platform_0201001_block_trsm_multi;
+    p.block_trsm_multi_trans = pangulu_platform_0201001_block_trsm_multi_trans;
     p.block_spmv_add = pangulu_platform_0201001_block_spmv_add;
     p.schedule = pangulu_platform_0201001_schedule;
     p.schedule_range = pangulu_platform_0201001_schedule_range;
@@ -172,6 +173,33 @@ void solution_from_factor_space(const Solver &S, const val_t *b, val_t *rhs)
     for (u32 i = 0; i < S.n_user; i++)
         rhs[S.match_col[i]] = value_times(y[i], S.scale_col[S.match_col[i]]);
 }
+// The transposed pair (pangulu_amd_gstrs_trans).  The factors are those of Ap = P A1 P^T with perm[new] = old, and on a handle with
+// scaling on A1 = Dr A Q Dc, that is A1[i, j] = dr[i] A[i, q(j)] dc[q(j)] with q = match_col.  For A^T x = b:
+//     (A1^T z)[j] = sum_i A1[i, j] z[i] = dc[q(j)] sum_i A[i, q(j)] (dr[i] z[i]) = dc[q(j)] (A^T x)[q(j)]   with x[i] = dr[i] z[i],
+// so A1^T z = c with c[j] = dc[q(j)] b[q(j)] gives x = Dr z: the roles of the scalings swap, and the matching moves to the way in
+// (b lives in the column space of A, z in its row space).  Dr and Dc are real, so A^H x = b takes the same pair.  The symmetric
+// permutation is the same as above: Ap^T = P A1^T P^T; a padding row stays 1 * z = 0.
+void rhs_to_factor_space_trans(const Solver &S, const val_t *rhs, val_t *b)
+{
+    const bool scaled = !S.scale_row.empty();
+    for (u32 i = 0; i < S.n; i++)
+    {
+        const u32 j = S.perm[i]; // column of A1
+        if (j >= S.n_user)
+            memset(&b[i], 0, sizeof(val_t));
+        else if (scaled)
+            b[i] = value_times(rhs[S.match_col[j]], S.scale_col[S.match_col[j]]); // c[j] = dc[q(j)] b[q(j)]
+        else
+            b[i] = rhs[j];
+    }
+}
+void solution_from_factor_space_trans(const Solver &S, const val_t *b, val_t *rhs)
+{
+    const bool scaled = !S.scale_row.empty();
+    for (u32 i = 0; i < S.n; i++)
+        if (S.perm[i] < S.n_user)
+            rhs[S.perm[i]] = scaled ? value_times(b[i], S.scale_row[S.perm[i]]) : b[i]; // x = Dr z
+}
 } // namespace
 
 extern "C"
@@ -228,6 +256,10 @@ extern "C"
         p.sptrsv = (void (*)(pangulu_inblock_idx, slot_t *, val_t *, pangulu_int64_t))get("sptrsv");
         if (missing)
             return 2;
+        // optional extension: a platform without it leaves the transposed solve to the host sweep
+        snprintf(sym, sizeof(sym), "pangulu_platform_%07x_block_trsm_multi_trans", platform_id);
+        p.block_trsm_multi_trans = (int (*)(pangulu_inblock_idx, const pangulu_hip_solve_sweep_t *, const pangulu_hip_solve_sweep_t *, int, val_t *,
+                                            pangulu_uint64_t, pangulu_uint64_t, const int *))dlsym(h, sym);
         int (*sz)() = (int (*)())dlsym(h, "pangulu_oracle_sizeof_value");
         if (sz && sz() != (int)sizeof(val_t))
         {
@@ -750,6 +782,58 @@ extern "C"
         if (comm->rank == 0)
             for (sparse_index_t j = 0; j < nrhs; j++)
                 solution_from_factor_space(*S, b.data() + (size_t)j * S->n, rhs + (size_t)j * ldb);
+        S->info.time_solve = wall_seconds() - t0;
+        return 0;
+    }
+
+    int pangulu_amd_gstrs_trans(sparse_value_t *rhs, sparse_index_t nrhs, sparse_pointer_t ldb, int trans, pangulu_gstrs_options *gstrs_options,
+                                void **pangulu_handle)
+    {
+        if (gstrs_options == nullptr)
+        {
+            if (world()->rank == 0)
+                printf("[PanguLU ERROR] Invalid input parameter. gstrs option struct pointer is NULL. Exit.\n");
+            exit(1);
+        }
+        Solver *S = (Solver *)*pangulu_handle;
+        if (!S->factored)
+            return 1;
+        const double t0 = wall_seconds();
+        Comm *comm = world();
+        // rank 0's arguments decide for everybody
+        unsigned long long head[3] = {0, (unsigned long long)nrhs, (unsigned long long)(unsigned)trans};
+        if (comm->rank == 0)
+        {
+            if (trans != PANGULU_AMD_TRANS_NONE && trans != PANGULU_AMD_TRANS_T && trans != PANGULU_AMD_TRANS_H)
+                head[0] = 3;
+            else if (nrhs != 0 && (rhs == nullptr || ldb < (sparse_pointer_t)S->n_user))
+                head[0] = 2;
+        }
+        comm->bcast(head, sizeof(head), 0);
+        if (head[0] != 0)
+            return (int)head[0];
+        trans = (int)head[2];
+        if (trans == PANGULU_AMD_TRANS_NONE)
+            return pangulu_amd_gstrs_multi(rhs, nrhs, ldb, gstrs_options, pangulu_handle);
+        NearDevice near(active_platform());
+        nrhs = (sparse_index_t)head[1];
+        if (nrhs == 0)
+            return 0;
+        std::vector<val_t> b((size_t)S->n * nrhs);
+        if (comm->rank == 0)
+            for (sparse_index_t j = 0; j < nrhs; j++)
+                rhs_to_factor_space_trans(*S, rhs + (size_t)j * ldb, b.data() + (size_t)j * S->n);
+        comm->bcast(b.data(), sizeof(val_t) * b.size(), 0);
+        comm->barrier();
+#ifdef PANGULU_COMPLEX
+        const bool conjugate = trans == PANGULU_AMD_TRANS_H;
+#else
+        const bool conjugate = false; // real values: A^H = A^T
+#endif
+        triangular_solve_multi_trans(*S, b.data(), (u32)nrhs, conjugate);
+        if (comm->rank == 0)
+            for (sparse_index_t j = 0; j < nrhs; j++)
+                solution_from_factor_space_trans(*S, b.data() + (size_t)j * S->n, rhs + (size_t)j * ldb);
         S->info.time_solve = wall_seconds() - t0;
         return 0;
     }

@@ -83,6 +83,9 @@ struct Platform
                            const val_t *, val_t *, pangulu_uint64_t) = nullptr;
     int (*block_trsm_multi)(pangulu_inblock_idx, const pangulu_hip_solve_sweep_t *, const pangulu_hip_solve_sweep_t *, val_t *, pangulu_uint64_t,
                             pangulu_uint64_t, const int *) = nullptr;
+    // optional: the transposed solve on the device (0 returned: not offered at this nb / with these switches)
+    int (*block_trsm_multi_trans)(pangulu_inblock_idx, const pangulu_hip_solve_sweep_t *, const pangulu_hip_solve_sweep_t *, int, val_t *,
+                                  pangulu_uint64_t, pangulu_uint64_t, const int *) = nullptr;
 };
 Platform &active_platform();               // built-in HIP unless the test hook replaced it
 bool platform_is_builtin_hip();
@@ -359,6 +362,9 @@ struct Solver
     // same pattern keep them: the records stay where they are); and what the last pangulu_amd_gstrs_multi did (pangulu_amd_last_solve_path)
     SolveSweepPlan solve_plan[2];
     bool solve_plan_ready = false;
+    // the transposed solve's plans (pangulu_amd_gstrs_trans): [0] forward with U^T, [1] backward with L^T, from the block-CSC side
+    SolveSweepPlan solve_plan_trans[2];
+    bool solve_plan_trans_ready = false;
     int last_solve_device_columns = 0, last_solve_panel_width = 0, last_solve_panels = 0;
     // Multi-rank replay (round 4, PANGULU_AMD_MULTI_REPLAY=1): what THIS rank did in its first factorisation, in order -- the ranges
     // of the back-end's recorded operations its platform calls produced, the markers between them with the blocks that were
@@ -443,6 +449,9 @@ void record_schedule(Solver &S);                          // pangulu_init, one r
 void download_factors(Solver &S);                         // device -> host mirror of owned values
 void triangular_solve(Solver &S, val_t *rhs_permuted);    // forward + backward block sweeps (host kernels)
 void triangular_solve_multi(Solver &S, val_t *B, u32 nrhs); // the same for n x nrhs permuted values, column j at B + j n: panels on the device, or the sweep above per column
+// A^T X = B (conjugate = false) or A^H X = B on the same factors, same layout and collectiveness as triangular_solve_multi: panels
+// through Platform::block_trsm_multi_trans where the device solve runs and offers it, the host sweep over block columns elsewhere
+void triangular_solve_multi_trans(Solver &S, val_t *B, u32 nrhs, bool conjugate);
 double factor_check(Solver &S);                           // ||L(U 1) - A 1|| / ||A 1|| on the factors where they are (pg_check.cpp; collective)
 double factor_check_vectors(Solver &S, int nvec, unsigned long long seed); // the same on the ones vector + nvec - 1 random +-1 vectors: the worst quotient
 void compute_task_model(Solver &S, double hbm_bytes_per_s, double fp_flops_per_s); // pg_model.cpp: T* of SURVEY.md §8d

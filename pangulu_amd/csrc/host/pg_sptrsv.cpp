@@ -26,6 +26,7 @@ inline val_t vdiv(val_t a, val_t b)
 }
 inline double vreal(val_t a) { return (double)a.re; }
 inline val_t vmake(double r) { return val_t{(calculate_real_type)r, 0}; }
+inline val_t vop(val_t a, bool conj) { return conj ? val_t{a.re, -a.im} : a; }
 #else
 inline val_t vmul(val_t a, val_t b) { return a * b; }
 inline val_t vsub(val_t a, val_t b) { return a - b; }
@@ -33,6 +34,7 @@ inline val_t vadd(val_t a, val_t b) { return a + b; }
 inline val_t vdiv(val_t a, val_t b) { return a / b; }
 inline double vreal(val_t a) { return (double)a; }
 inline val_t vmake(double r) { return (val_t)r; }
+inline val_t vop(val_t a, bool) { return a; }
 #endif
 
 // y -= A x for a CSC block
@@ -68,6 +70,47 @@ void block_upper_solve(u32 nb, const slot_t *u, val_t *x)
             acc = vsub(acc, vmul(u->value[p], x[u->rowindex[p]]));
         val_t d = u->value[b];
         x[r] = (std::fabs(vreal(d)) > PANGULU_SPTRSV_TOL) ? vdiv(acc, d) : vdiv(acc, vmake(PANGULU_SPTRSV_TOL));
+    }
+}
+
+// The in-block routines of the transposed sweeps; op() conjugates for A^H.
+// y -= op(A)^T x for a CSC block: column c of A is row c of A^T
+void block_spmv_trans(u32 nb, const slot_t *a, const val_t *x, val_t *y, bool conj)
+{
+    for (u32 c = 0; c < nb; c++)
+    {
+        val_t acc = y[c];
+        for (u32 p = a->columnpointer[c]; p < a->columnpointer[c + 1]; p++)
+            acc = vsub(acc, vmul(vop(a->value[p], conj), x[a->rowindex[p]]));
+        y[c] = acc;
+    }
+}
+
+// forward solve with op(U)^T from the CSR record of U (diagonal first): row r of U is column r of U^T
+void block_upper_trans_solve(u32 nb, const slot_t *u, val_t *x, bool conj)
+{
+    for (u32 r = 0; r < nb; r++)
+    {
+        u32 b = u->columnpointer[r], e = u->columnpointer[r + 1];
+        if (b == e)
+            continue;
+        val_t d = vop(u->value[b], conj);
+        val_t xr = (std::fabs(vreal(d)) > PANGULU_SPTRSV_TOL) ? vdiv(x[r], d) : vdiv(x[r], vmake(PANGULU_SPTRSV_TOL));
+        x[r] = xr;
+        for (u32 p = b + 1; p < e; p++)
+            x[u->rowindex[p]] = vsub(x[u->rowindex[p]], vmul(vop(u->value[p], conj), xr));
+    }
+}
+
+// backward solve with op(L)^T (unit diagonal) from the strictly-lower CSC record of L: column c of L is row c of L^T
+void block_lower_trans_solve(u32 nb, const slot_t *l, val_t *x, bool conj)
+{
+    for (i64 c = (i64)nb - 1; c >= 0; c--)
+    {
+        val_t acc = x[c];
+        for (u32 p = l->columnpointer[c]; p < l->columnpointer[c + 1]; p++)
+            acc = vsub(acc, vmul(vop(l->value[p], conj), x[l->rowindex[p]]));
+        x[c] = acc;
     }
 }
 
@@ -125,6 +168,57 @@ static void build_sweep_plan(const Solver &S, bool lower, SolveSweepPlan &plan)
     }
 }
 
+// The same for the transposed solve, from the block-CSC side of the pattern: block row i of U^T is block column i of U, so in the
+// forward sweep (U^T) segment i reads the segments k < i of the blocks A(k, i), and in the backward sweep (L^T) the segments k > i.
+// `brow` of a row is the destination segment i, blk_bcol the source segment k, `diag` the upper half (forward) / the lower half.
+static void build_trans_sweep_plan(const Solver &S, bool forward, SolveSweepPlan &plan)
+{
+    const BlockPattern &P = S.pat;
+    const u32 nbk = S.nbk;
+    auto begin_of = [&](u32 i) { return forward ? P.colptr[i] : P.first_after_diag[i]; };
+    auto end_of = [&](u32 i) { return forward ? P.first_after_diag[i] : P.colptr[i + 1]; };
+    std::vector<u32> level(nbk, 0);
+    u32 nlevel = 0;
+    for (u32 step = 0; step < nbk; step++)
+    {
+        const u32 i = forward ? step : nbk - 1 - step;
+        u32 lv = 0;
+        for (u64 b = begin_of(i); b < end_of(i); b++)
+            lv = std::max(lv, level[P.rowidx[b]] + 1);
+        level[i] = lv;
+        nlevel = std::max(nlevel, lv + 1);
+    }
+    plan.nlevel = nlevel;
+    plan.level_ptr.assign((size_t)nlevel + 1, 0);
+    for (u32 k = 0; k < nbk; k++)
+        plan.level_ptr[level[k] + 1]++;
+    for (u32 l = 0; l < nlevel; l++)
+        plan.level_ptr[l + 1] += plan.level_ptr[l];
+    plan.rows.assign(nbk, pangulu_hip_solve_row_t());
+    plan.blk_slots.clear();
+    plan.blk_bcol.clear();
+    std::vector<pangulu_uint64_t> cur(plan.level_ptr.begin(), plan.level_ptr.end() - 1);
+    for (u32 i = 0; i < nbk; i++)
+    {
+        pangulu_hip_solve_row_t R;
+        R.brow = i;
+        R.first = plan.blk_slots.size();
+        R.diag = forward ? S.diag_upper[i] : S.diag_lower[i];
+        for (u64 b = begin_of(i); b < end_of(i); b++)
+        {
+            plan.blk_slots.push_back(S.slot_of[b]);
+            plan.blk_bcol.push_back(P.rowidx[b]);
+        }
+        R.nblk = (pangulu_exblock_idx)(plan.blk_slots.size() - R.first);
+        plan.rows[cur[level[i]]++] = R;
+    }
+    if (plan.blk_slots.empty())
+    {
+        plan.blk_slots.push_back(nullptr);
+        plan.blk_bcol.push_back(0);
+    }
+}
+
 // one rank, a device platform, PANGULU_AMD_DEVICE_SOLVE not 0
 static bool device_solve_enabled(const Solver &S, const Platform &plat)
 {
@@ -135,19 +229,26 @@ static bool device_solve_enabled(const Solver &S, const Platform &plat)
 // Single rank on a device: both sweeps on the device-resident factors (no download of the factors), level by level of the block
 // dependency graph.  X holds `npanel` panels one after the other, panel p with nbk*nb x w[p] values, right-hand side fastest: one
 // pangulu_platform_0201001_block_trsm_multi call; a platform with block_trsv alone takes single columns (w[p] = 1), sweep by sweep.
-// The plans of both sweeps are built on first use and kept on the handle.
-static void device_solve_panels(Solver &S, Platform &plat, val_t *X, size_t npanel, const int *w)
+// The plans of both sweeps are built on first use and kept on the handle.  trans = PANGULU_AMD_TRANS_T / _H: the transposed sweeps
+// (U^T forward, L^T backward) on plans of their own through Platform::block_trsm_multi_trans, which the caller has found to be offered.
+static void device_solve_panels(Solver &S, Platform &plat, val_t *X, size_t npanel, const int *w, int trans = PANGULU_AMD_TRANS_NONE)
 {
-    if (!S.solve_plan_ready)
+    if (trans == PANGULU_AMD_TRANS_NONE && !S.solve_plan_ready)
     {
         build_sweep_plan(S, true, S.solve_plan[0]);
         build_sweep_plan(S, false, S.solve_plan[1]);
         S.solve_plan_ready = true;
     }
+    if (trans != PANGULU_AMD_TRANS_NONE && !S.solve_plan_trans_ready)
+    {
+        build_trans_sweep_plan(S, true, S.solve_plan_trans[0]);
+        build_trans_sweep_plan(S, false, S.solve_plan_trans[1]);
+        S.solve_plan_trans_ready = true;
+    }
     pangulu_hip_solve_sweep_t sw[2];
     for (int s = 0; s < 2; s++)
     {
-        const SolveSweepPlan &pl = S.solve_plan[s];
+        const SolveSweepPlan &pl = trans == PANGULU_AMD_TRANS_NONE ? S.solve_plan[s] : S.solve_plan_trans[s];
         sw[s].nlevel = pl.nlevel;
         sw[s].level_ptr = pl.level_ptr.data();
         sw[s].rows = pl.rows.data();
@@ -155,6 +256,11 @@ static void device_solve_panels(Solver &S, Platform &plat, val_t *X, size_t npan
         sw[s].blk_bcol = pl.blk_bcol.data();
     }
     const pangulu_uint64_t xlen = (pangulu_uint64_t)S.nbk * S.nb;
+    if (trans != PANGULU_AMD_TRANS_NONE)
+    {
+        plat.block_trsm_multi_trans((pangulu_inblock_idx)S.nb, &sw[0], &sw[1], trans == PANGULU_AMD_TRANS_H, X, xlen, (pangulu_uint64_t)npanel, w);
+        return;
+    }
     if (plat.block_trsm_multi)
     {
         plat.block_trsm_multi((pangulu_inblock_idx)S.nb, &sw[0], &sw[1], X, xlen, (pangulu_uint64_t)npanel, w);
@@ -244,23 +350,11 @@ void triangular_solve(Solver &S, val_t *rhs)
     std::copy(x.begin(), x.begin() + S.n, rhs);
 }
 
-// Panels of right-hand sides through pangulu_platform_0201001_block_trsm_multi where the device solve runs, triangular_solve()
-// column by column everywhere else (N > 1 ranks, host-memory platforms, PANGULU_AMD_DEVICE_SOLVE=0): collective, same tags.
-void triangular_solve_multi(Solver &S, val_t *Bm, u32 nrhs)
+// the columns of Bm in panels through the device sweeps (trans: which pair), panels at most wmax wide
+static void device_solve_columns(Solver &S, Platform &plat, val_t *Bm, u32 nrhs, int wmax, int trans)
 {
-    Platform &plat = active_platform();
-    S.last_solve_device_columns = 0;
-    S.last_solve_panel_width = 1;
-    S.last_solve_panels = (int)nrhs;
-    if (!device_solve_enabled(S, plat) || !plat.block_trsm_multi)
-    {
-        for (u32 j = 0; j < nrhs; j++)
-            triangular_solve(S, Bm + (size_t)j * S.n);
-        return;
-    }
     S.last_solve_device_columns = (int)nrhs;
     const u32 nb = S.nb, n = S.n;
-    const int wmax = plat.block_trsm_multi((pangulu_inblock_idx)nb, nullptr, nullptr, nullptr, 0, 0, nullptr);
     // panels: the widest width while that many columns are left, then the smallest power of two that holds the rest (zero columns pad it)
     std::vector<int> w;
     size_t total_w = 0;
@@ -295,7 +389,7 @@ void triangular_solve_multi(Solver &S, val_t *Bm, u32 nrhs)
                        for (u32 i = 0; i < n; i++)
                            Xp[(size_t)i * wp + r] = col[i];
                    } });
-    device_solve_panels(S, plat, X.data(), w.size(), w.data());
+    device_solve_panels(S, plat, X.data(), w.size(), w.data(), trans);
     each_panel([&](val_t *Xp, int wp, u32 j0, u32 nc)
                {
                    for (u32 r = 0; r < nc; r++)
@@ -306,6 +400,110 @@ void triangular_solve_multi(Solver &S, val_t *Bm, u32 nrhs)
                    } });
     S.last_solve_panel_width = w[0];
     S.last_solve_panels = (int)w.size();
+}
+
+// Panels of right-hand sides through pangulu_platform_0201001_block_trsm_multi where the device solve runs, triangular_solve()
+// column by column everywhere else (N > 1 ranks, host-memory platforms, PANGULU_AMD_DEVICE_SOLVE=0): collective, same tags.
+void triangular_solve_multi(Solver &S, val_t *Bm, u32 nrhs)
+{
+    Platform &plat = active_platform();
+    S.last_solve_device_columns = 0;
+    S.last_solve_panel_width = 1;
+    S.last_solve_panels = (int)nrhs;
+    if (!device_solve_enabled(S, plat) || !plat.block_trsm_multi)
+    {
+        for (u32 j = 0; j < nrhs; j++)
+            triangular_solve(S, Bm + (size_t)j * S.n);
+        return;
+    }
+    const int wmax = plat.block_trsm_multi((pangulu_inblock_idx)S.nb, nullptr, nullptr, nullptr, 0, 0, nullptr);
+    device_solve_columns(S, plat, Bm, nrhs, wmax, PANGULU_AMD_TRANS_NONE);
+}
+
+// The host sweep of the transposed solve for one vector, everywhere the device solve does not run: the loop of triangular_solve()
+// over block COLUMNS.  Forward with U^T: segment i receives -op(U(k, i))^T x_k from the blocks k < i of block column i, whose owners
+// contribute; the diagonal owner sums the partial vectors (tags of their own), solves with the transpose of its upper half and
+// broadcasts the segment.  Backward with L^T: the blocks k > i and the transpose of the unit lower half.
+static void triangular_solve_trans(Solver &S, val_t *rhs, bool conj)
+{
+    download_factors(S);
+    Comm *comm = world();
+    const BlockPattern &P = S.pat;
+    u32 nb = S.nb, nbk = S.nbk;
+    int me = S.rank;
+    std::vector<char> contributes((size_t)S.nproc, 0);
+    std::vector<val_t> x((size_t)nbk * nb, vmake(0)), acc(nb), tmp(nb);
+    std::copy(rhs, rhs + S.n, x.begin());
+    const int TAG_PART_TRANS = 0x200000;
+
+    for (int pass = 0; pass < 2; pass++)
+    {
+        bool forward = pass == 0;
+        for (u32 step = 0; step < nbk; step++)
+        {
+            u32 bcol = forward ? step : nbk - 1 - step;
+            val_t *seg = x.data() + (size_t)bcol * nb;
+            int diag_rank = S.owner(bcol, bcol);
+            u64 cb = forward ? P.colptr[bcol] : P.first_after_diag[bcol];
+            u64 ce = forward ? P.first_after_diag[bcol] : P.colptr[bcol + 1];
+            std::fill(contributes.begin(), contributes.end(), 0);
+            for (u64 b = cb; b < ce; b++)
+                contributes[(size_t)S.owner(P.rowidx[b], bcol)] = 1;
+            if (contributes[(size_t)me] || me == diag_rank)
+            {
+                std::fill(acc.begin(), acc.end(), vmake(0));
+                for (u64 b = cb; b < ce; b++)
+                {
+                    u32 brow = P.rowidx[b];
+                    if (S.owner(brow, bcol) != me)
+                        continue;
+                    block_spmv_trans(nb, S.slot_of[b], x.data() + (size_t)brow * nb, acc.data(), conj);
+                }
+                if (me == diag_rank)
+                {
+                    for (int r = 0; r < S.nproc; r++)
+                    {
+                        if (r == me || !contributes[(size_t)r])
+                            continue;
+                        comm->recv_bytes(r, TAG_PART_TRANS + (int)(bcol & 0xfffff), tmp.data(), sizeof(val_t) * nb);
+                        for (u32 i = 0; i < nb; i++)
+                            acc[i] = vadd(acc[i], tmp[i]);
+                    }
+                    for (u32 i = 0; i < nb; i++)
+                        seg[i] = vadd(seg[i], acc[i]);
+                    if (forward)
+                        block_upper_trans_solve(nb, S.diag_upper[bcol], seg, conj);
+                    else
+                        block_lower_trans_solve(nb, S.diag_lower[bcol], seg, conj);
+                }
+                else
+                {
+                    comm->send_bytes(diag_rank, TAG_PART_TRANS + (int)(bcol & 0xfffff), acc.data(), sizeof(val_t) * nb);
+                }
+            }
+            comm->bcast(seg, sizeof(val_t) * nb, diag_rank);
+        }
+        comm->barrier();
+    }
+    std::copy(x.begin(), x.begin() + S.n, rhs);
+}
+
+void triangular_solve_multi_trans(Solver &S, val_t *Bm, u32 nrhs, bool conjugate)
+{
+    Platform &plat = active_platform();
+    S.last_solve_device_columns = 0;
+    S.last_solve_panel_width = 1;
+    S.last_solve_panels = (int)nrhs;
+    int wmax = 0;
+    if (device_solve_enabled(S, plat) && plat.block_trsm_multi_trans)
+        wmax = plat.block_trsm_multi_trans((pangulu_inblock_idx)S.nb, nullptr, nullptr, 0, nullptr, 0, 0, nullptr);
+    if (wmax < 1)
+    {
+        for (u32 j = 0; j < nrhs; j++)
+            triangular_solve_trans(S, Bm + (size_t)j * S.n, conjugate);
+        return;
+    }
+    device_solve_columns(S, plat, Bm, nrhs, wmax, conjugate ? PANGULU_AMD_TRANS_H : PANGULU_AMD_TRANS_T);
 }
 
 } // namespace pg

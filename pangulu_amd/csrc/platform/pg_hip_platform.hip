@@ -87,6 +87,7 @@ __host__ __device__ inline val_t v_div(val_t a, val_t b)
     return val_t{(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
 }
 __host__ __device__ inline real_t v_realpart(val_t a) { return a.re; }
+__host__ __device__ inline val_t v_conj(val_t a) { return val_t{a.re, -a.im}; }
 #else
 __host__ __device__ inline val_t v_make(real_t r) { return r; }
 __host__ __device__ inline val_t v_mul(val_t a, val_t b) { return a * b; }
@@ -94,6 +95,7 @@ __host__ __device__ inline val_t v_sub(val_t a, val_t b) { return a - b; }
 __host__ __device__ inline val_t v_submul(val_t a, val_t b, val_t c) { return a - b * c; } // contracts to one FMA
 __host__ __device__ inline val_t v_div(val_t a, val_t b) { return a / b; }
 __host__ __device__ inline real_t v_realpart(val_t a) { return a; }
+__host__ __device__ inline val_t v_conj(val_t a) { return a; }
 #endif
 
 // LDS accumulator -= v with hardware floating-point atomics
@@ -801,14 +803,29 @@ namespace
 
 #include "pg_hip_block_solve.h"
 #include "pg_hip_block_solve_multi.h"
+#include "pg_hip_block_solve_trans.h"
 
 #include "pg_hip_backend.h"
 
+// What a sweep does with its records: L (unit, forward), U (backward), or -- the transposed solve, pg_hip_block_solve_trans.h --
+// U^T (forward, on the upper halves) and L^T (backward, on the lower halves), with SOLVE_CONJ added for A^H.
+enum
+{
+    SOLVE_LOWER = 0,
+    SOLVE_UPPER = 1,
+    SOLVE_UT = 2,
+    SOLVE_LT = 3,
+    SOLVE_CONJ = 4
+};
+inline bool solve_mode_upper_half(int mode) { return (mode & 3) == SOLVE_UPPER || (mode & 3) == SOLVE_UT; }
+
 // device-side descriptors of one sweep, appended to hr / hb: rows keep their order, the blocks of level l are
-// hb[blk_level_ptr[l] .. blk_level_ptr[l + 1]) counted from the first block appended here
-void append_solve_descriptors(int upper, const pangulu_hip_solve_sweep_t &sw, std::vector<SolveRowD> &hr, std::vector<SolveBlkD> &hb,
+// hb[blk_level_ptr[l] .. blk_level_ptr[l + 1]) counted from the first block appended here.  `mode`: see above (a transposed
+// sweep's rows are destination segments, blk_bcol its blocks' source segments: the descriptors are the same)
+void append_solve_descriptors(int mode, const pangulu_hip_solve_sweep_t &sw, std::vector<SolveRowD> &hr, std::vector<SolveBlkD> &hb,
                               std::vector<size_t> &blk_level_ptr)
 {
+    const bool upper = solve_mode_upper_half(mode);
     const size_t r0 = hr.size(), b0 = hb.size();
     hr.resize(r0 + (size_t)sw.level_ptr[sw.nlevel]);
     blk_level_ptr.assign((size_t)sw.nlevel + 1, 0);
@@ -863,11 +880,37 @@ int solve_widest_panel(size_t nb)
 // what one sweep of a solve call has on the device: its rows and blocks start at row0 / blk0 of the call's descriptor arrays
 struct SolveSweepD
 {
-    int upper;
+    int upper; // SOLVE_LOWER / SOLVE_UPPER, or a transposed mode
     const pangulu_hip_solve_sweep_t *sw;
     size_t row0, blk0;
     std::vector<size_t> blk_level_ptr;
 };
+
+// one level of a transposed sweep: the gather over the level's blocks, then its diagonal halves.  Every instantiation keeps its own
+// record of the dynamic LDS it has been allowed.
+template <int W, bool CONJ>
+void launch_solve_trans_level(bool lt, int nb, int ch, size_t nbl, size_t n, const SolveBlkD *blks, const SolveRowD *rows, val_t *d_x)
+{
+    const size_t lds_gather = solve_trans_lds_gather((size_t)nb, W), lds_level = solve_multi_lds_level((size_t)nb, W, ch);
+    static size_t allowed_gather = 0, allowed_level = 0;
+    if (lds_gather > allowed_gather)
+    {
+        HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_gather_trans_kernel<W, CONJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gather));
+        allowed_gather = lds_gather;
+    }
+    if (lds_level > allowed_level)
+    {
+        HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_trans_kernel<false, W, CONJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
+        HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_trans_kernel<true, W, CONJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
+        allowed_level = lds_level;
+    }
+    if (nbl)
+        hipLaunchKernelGGL((block_trsm_gather_trans_kernel<W, CONJ>), dim3((unsigned)nbl), dim3(256), lds_gather, B.stream, blks, nb, d_x);
+    if (lt)
+        hipLaunchKernelGGL((block_trsm_level_trans_kernel<true, W, CONJ>), dim3((unsigned)n), dim3(256), lds_level, B.stream, rows, nb, d_x, ch);
+    else
+        hipLaunchKernelGGL((block_trsm_level_trans_kernel<false, W, CONJ>), dim3((unsigned)n), dim3(256), lds_level, B.stream, rows, nb, d_x, ch);
+}
 
 // the launches of one panel of W right-hand sides in d_x: the sweeps one after the other, a gather and a level launch per level
 template <int W>
@@ -900,6 +943,16 @@ void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, const So
                 continue;
             const SolveBlkD *blks = d_blks + S.blk0 + S.blk_level_ptr[l];
             const SolveRowD *rows = d_rows + S.row0 + lp[l];
+            if ((S.upper & 3) >= SOLVE_UT) // (the operator offers no transposed sweep where the column-by-column pair would run)
+            {
+#ifdef PANGULU_COMPLEX
+                if (S.upper & SOLVE_CONJ)
+                    launch_solve_trans_level<W, true>((S.upper & 3) == SOLVE_LT, nb, ch, nbl, n, blks, rows, d_x);
+                else
+#endif
+                    launch_solve_trans_level<W, false>((S.upper & 3) == SOLVE_LT, nb, ch, nbl, n, blks, rows, d_x);
+                continue;
+            }
             if (by_column)
             {
                 const size_t lds = sizeof(val_t) * (size_t)nb;
@@ -921,7 +974,7 @@ void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, const So
 }
 
 // The level-scheduled block triangular solve, both operators' body: the descriptors of the given sweeps (one, or the lower and then
-// the upper one) go up once; the panels of the HOST buffer X (panel p: xlen x w[p] values, right-hand side fastest, w[p] a width
+// the upper one; or U^T and then L^T) go up once; the panels of the HOST buffer X (panel p: xlen x w[p] values, right-hand side fastest, w[p] a width
 // solve_widest_panel() allows) then pass through one device buffer one after the other: upload, the sweeps, download.
 void block_solve_panels(int nb, const std::vector<const pangulu_hip_solve_sweep_t *> &sw, const std::vector<int> &upper, val_t *X, size_t xlen, size_t npanel,
                         const int *w)
@@ -1713,6 +1766,33 @@ extern "C"
                 exit(EXIT_FAILURE);
             }
         block_solve_panels((int)nb, {lower, upper}, {0, 1}, X, (size_t)xlen, (size_t)npanel, w);
+        return wmax;
+    }
+
+    // The transposed solve: a forward sweep with U^T, then a backward sweep with L^T (pg_hip_block_solve_trans.h), through the same
+    // launch routine.  0: no transposed kernels here (the column-by-column pair has no transposed twin).
+    int pangulu_platform_0201001_block_trsm_multi_trans(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *forward_ut,
+                                                        const pangulu_hip_solve_sweep_t *backward_lt, int conjugate, calculate_type *X,
+                                                        pangulu_uint64_t xlen, pangulu_uint64_t npanel, const int *w)
+    {
+        if (solve_by_column(nb))
+            return 0;
+        const int wmax = solve_widest_panel(nb);
+        if (npanel == 0)
+            return wmax;
+        for (size_t p = 0; p < (size_t)npanel; p++)
+            if (w[p] < 1 || w[p] > wmax || (w[p] & (w[p] - 1)))
+            {
+                fprintf(stderr, "[PanguLU-AMD ERROR] block_trsm_multi_trans: panel width %d (nb = %d takes powers of two up to %d)\n", w[p], (int)nb, wmax);
+                exit(EXIT_FAILURE);
+            }
+#ifdef PANGULU_COMPLEX
+        const int conj = conjugate ? SOLVE_CONJ : 0;
+#else
+        const int conj = 0; // (real values: A^H = A^T)
+        (void)conjugate;
+#endif
+        block_solve_panels((int)nb, {forward_ut, backward_lt}, {SOLVE_UT | conj, SOLVE_LT | conj}, X, (size_t)xlen, (size_t)npanel, w);
         return wmax;
     }
 

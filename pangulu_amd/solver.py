@@ -92,17 +92,39 @@ def pangulu_gstrf(h):
     h.lib.pangulu_gstrf(ctypes.byref(opt), h.ref)
 
 
-def pangulu_gstrs(h, rhs):
-    """Solves A x = rhs with the factors; returns x (rank 0; other ranks get their input back)."""
+TRANS = {"N": 0, "T": 1, "H": 2}  # PANGULU_AMD_TRANS_*
+
+
+def _trans_code(trans):
+    if trans not in TRANS:
+        raise ValueError("trans must be 'N', 'T' or 'H', got %r" % (trans,))
+    return TRANS[trans]
+
+
+_GSTRS_ERRORS = {1: "the handle has not been factorised", 2: "bad rhs / ldb", 3: "unknown trans"}
+
+
+def pangulu_gstrs(h, rhs, trans="N"):
+    """Solves A x = rhs (trans="N"), A^T x = rhs ("T") or A^H x = rhs ("H") with the factors; returns x (rank 0; other ranks get
+    their input back)."""
+    code = _trans_code(trans)
     opt = _lib.GstrsOptions()
     x = np.array(rhs, dtype=h.dtype, copy=True) if rhs is not None else np.zeros(h.n, dtype=h.dtype)
-    h.lib.pangulu_gstrs(x.ctypes.data_as(ctypes.c_void_p), ctypes.byref(opt), h.ref)
+    if code == 0:
+        h.lib.pangulu_gstrs(x.ctypes.data_as(ctypes.c_void_p), ctypes.byref(opt), h.ref)
+        return x
+    rc = h.lib.pangulu_amd_gstrs_trans(x.ctypes.data_as(ctypes.c_void_p), 1, h.n, code, ctypes.byref(opt), h.ref)
+    if rc != 0:
+        raise RuntimeError("pangulu_amd_gstrs_trans failed (%d): %s" % (rc, _GSTRS_ERRORS.get(rc, "?")))
     return x
 
 
-def pangulu_gstrs_multi(h, B, nrhs=None):
-    """Solves A X = B for all columns of B, shape (n, nrhs) in any memory order, with one pass over the factors per panel of
-    columns (pangulu_amd_gstrs_multi); returns X of the same shape (rank 0).  Other ranks pass None and nrhs."""
+def pangulu_gstrs_multi(h, B, nrhs=None, trans="N"):
+    """Solves A X = B (trans="N"), A^T X = B ("T") or A^H X = B ("H") for all columns of B, shape (n, nrhs) in any memory order, with
+    one pass over the factors per panel of columns (pangulu_amd_gstrs_multi / pangulu_amd_gstrs_trans); returns X of the same shape
+    (rank 0).  Other ranks pass None and nrhs, and "N" exactly where rank 0 does (it selects the entry point; between "T" and "H"
+    rank 0 decides)."""
+    code = _trans_code(trans)
     opt = _lib.GstrsOptions()
     if B is not None:
         B = np.asarray(B)
@@ -113,6 +135,11 @@ def pangulu_gstrs_multi(h, B, nrhs=None):
         ptr = x.ctypes.data_as(ctypes.c_void_p)
     else:
         x, ptr = None, None
+    if code != 0:
+        rc = h.lib.pangulu_amd_gstrs_trans(ptr, int(nrhs), h.n, code, ctypes.byref(opt), h.ref)
+        if rc != 0:
+            raise RuntimeError("pangulu_amd_gstrs_trans failed (%d): %s" % (rc, _GSTRS_ERRORS.get(rc, "?")))
+        return x
     rc = h.lib.pangulu_amd_gstrs_multi(ptr, int(nrhs), h.n, ctypes.byref(opt), h.ref)
     if rc != 0:
         raise RuntimeError("pangulu_amd_gstrs_multi failed (%d): %s" % (rc, "the handle has not been factorised" if rc == 1 else "bad rhs / ldb"))
@@ -120,7 +147,7 @@ def pangulu_gstrs_multi(h, B, nrhs=None):
 
 
 def last_solve_path(h):
-    """What the last pangulu_gstrs_multi on this handle did: columns swept on the device (0: host sweep), the widest panel, the
+    """What the last pangulu_gstrs_multi (or transposed solve) on this handle did: columns swept on the device (0: host sweep), the widest panel, the
     number of panels."""
     d, w, p = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     h.lib.pangulu_amd_last_solve_path(h.ref, ctypes.byref(d), ctypes.byref(w), ctypes.byref(p))

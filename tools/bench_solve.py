@@ -1,11 +1,13 @@
 """One GPU, one handle: what a block of right-hand sides costs beside single pangulu_gstrs calls on the same factors.
 
-    python tools/bench_solve.py [--matrix elastic3d] [--size 48] [--nb 256] [--vtype r64] [--nrhs 1,4,16,64] [--repeats 5]
+    python tools/bench_solve.py [--matrix elastic3d] [--size 48] [--nb 256] [--vtype r64] [--nrhs 1,4,16,64] [--repeats 5] [--trans N|T|H]
 
 After pangulu_gstrf it times, in this process, the median of `repeats` single pangulu_gstrs calls and the median of `repeats`
 pangulu_gstrs_multi calls per nrhs, and prints one JSON line: the times, the time per column, the panels, the factor bytes a panel
 streams (info.owned_bytes: every record is read once per panel) and the bandwidth that implies.  The yardstick is nrhs single
-calls.  (Run it through `tools/gpu_job.sh solve`, which puts it under a time limit.)"""
+calls.  --trans T|H also times the transposed solves (A^T X = B, A^H X = B) of the same handle, the single call and every nrhs, beside
+their untransposed twins: a transposed sweep streams the same factor bytes, so the untransposed time of the same run is its yardstick
+(matrices here are symmetric or nearly so: the residual is that of the transposed system all the same).  (Run it through `tools/gpu_job.sh solve`, which puts it under a time limit.)"""
 import argparse
 import json
 import os
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--vtype", default="r64", choices=sorted(_lib.VALUE_TYPES))
     ap.add_argument("--nrhs", default="1,4,16,64")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--trans", default="N", choices=["N", "T", "H"])
     a = ap.parse_args()
     dt = _lib.VALUE_TYPES[a.vtype][0]
     cplx = np.issubdtype(dt, np.complexfloating)
@@ -65,6 +68,18 @@ def main():
     out = {"tool": "bench_solve", "matrix": "%s(%d)" % (a.matrix, a.size), "vtype": a.vtype, "n": n, "nb": a.nb, "gstrf_s": round(t_gstrf, 4),
            "owned_bytes": int(info["owned_bytes"]), "gstrs_single_s": round(t_single, 5),
            "gstrs_single_gbs": round(info["owned_bytes"] / t_single / 1e9, 1), "multi": []}
+    if a.trans != "N":
+        At = M.to_scipy(n, cp, ri, va).T.tocsc()
+        if a.trans == "H":
+            At = At.conj()
+
+        def trans_residual(x, b):
+            return float(np.linalg.norm(At @ x - b) / np.linalg.norm(b))
+
+        pa.pangulu_gstrs(h, b0, trans=a.trans)
+        t_single_t = median_of(lambda: pa.pangulu_gstrs(h, b0, trans=a.trans))
+        out.update({"trans": a.trans, "trans_single_s": round(t_single_t, 5), "trans_single_gbs": round(info["owned_bytes"] / t_single_t / 1e9, 1),
+                    "trans_single_vs_untransposed": round(t_single_t / t_single, 3)})
     for w in widths:
         Bw = np.asfortranarray(B[:, :w])
         X = pa.pangulu_gstrs_multi(h, Bw)
@@ -76,6 +91,14 @@ def main():
                              "factor_bytes_per_panel": int(info["owned_bytes"]), "implied_gbs": round(path["panels"] * info["owned_bytes"] / t / 1e9, 1),
                              "worst_residual": float("%.2e" % res),
                              "column0_vs_single": float("%.2e" % (np.abs(X[:, 0] - x_single).max() / np.abs(x_single).max()))})
+        if a.trans != "N":
+            Xt = pa.pangulu_gstrs_multi(h, Bw, trans=a.trans)
+            pt = pa.last_solve_path(h)
+            tt = median_of(lambda: pa.pangulu_gstrs_multi(h, Bw, trans=a.trans))
+            out["multi"][-1]["trans"] = {"seconds": round(tt, 5), "vs_untransposed": round(tt / t, 3), "device_columns": pt["device_columns"],
+                                         "panel_width": pt["panel_width"], "panels": pt["panels"],
+                                         "implied_gbs": round(pt["panels"] * info["owned_bytes"] / tt / 1e9, 1),
+                                         "worst_residual": float("%.2e" % max(trans_residual(Xt[:, j], Bw[:, j]) for j in range(w)))}
     pa.pangulu_finalize(h)
     print(json.dumps(out), flush=True)
 
