@@ -91,15 +91,7 @@ __global__ __launch_bounds__(256) void block_spmv_add_kernel(const SpmvBlkD *__r
         {
             val_t part = v_make(0);
             for (u32 p = p0 + l16; p < p1; p += 16)
-            {
-                const val_t m = v_mul(B.val[p], xs[B.idx[p]]);
-#ifdef PANGULU_COMPLEX
-                part.re += m.re;
-                part.im += m.im;
-#else
-                part += m;
-#endif
-            }
+                part = v_add(part, v_mul(B.val[p], xs[B.idx[p]]));
             v_atomic_add(&yd[c], part); // (16 partial sums per row)
         }
     }
@@ -140,34 +132,12 @@ __global__ __launch_bounds__(64) void block_trsv_level_kernel(const SolveRowD *_
                 const u32 b = R.dptr[r], e = R.dptr[r + 1];
                 if (b == e)
                     continue;
-#ifdef PANGULU_COMPLEX
                 val_t part = v_make(0);
                 for (u32 p = b + 1 + lane; p < e; p += 64)
-                {
-                    const val_t m = v_mul(R.dval[p], seg[R.didx[p]]);
-                    part.re += m.re;
-                    part.im += m.im;
-                }
-                for (int off = 32; off > 0; off >>= 1)
-                {
-                    part.re += __shfl_down(part.re, off, 64);
-                    part.im += __shfl_down(part.im, off, 64);
-                }
-#else
-                val_t part = 0;
-                for (u32 p = b + 1 + lane; p < e; p += 64)
-                    part += R.dval[p] * seg[R.didx[p]];
-                for (int off = 32; off > 0; off >>= 1)
-                    part += __shfl_down(part, off, 64);
-#endif
+                    part = v_add(part, v_mul(R.dval[p], seg[R.didx[p]]));
+                part = solve_group_sum<1>(part, 64);
                 if (lane == 0)
-                {
-                    val_t d = R.dval[b];
-                    const real_t dr = v_realpart(d);
-                    if (!((dr < 0 ? -dr : dr) > (real_t)PANGULU_SPTRSV_TOL))
-                        d = v_make((real_t)PANGULU_SPTRSV_TOL);
-                    seg[r] = v_div(v_sub(seg[r], part), d);
-                }
+                    seg[r] = v_div(v_sub(seg[r], part), solve_clamped_divisor(R.dval[b]));
                 wave_lds_fence();
             }
         }

@@ -1,7 +1,9 @@
 // pg_hip_block_solve_multi.h -- the device kernels of the level-scheduled block triangular solve: a PANEL of W right-hand sides per
 // launch, W = 1 for pangulu_gstrs and up to 16 for pangulu_amd_gstrs_multi (pangulu_platform_0201001_block_trsv and
-// ..._block_trsm_multi launch the same instances).  Included inside the anonymous namespace of pg_hip_platform.hip, after
-// pg_hip_block_solve.h (descriptors SolveBlkD / SolveRowD, the column-by-column kernels of PANGULU_HIP_SOLVE_CHUNKED=0).
+// ..._block_trsm_multi launch the same instances), and the same for the TRANSPOSED solve, A^T X = B and A^H X = B, on the records of
+// A = L U as they lie in HBM (pangulu_platform_0201001_block_trsm_multi_trans).  Included inside the anonymous namespace of
+// pg_hip_platform.hip, after pg_hip_block_solve.h (descriptors SolveBlkD / SolveRowD, the column-by-column kernels of
+// PANGULU_HIP_SOLVE_CHUNKED=0).
 #pragma once
 
 // -----------------------------------------------------------------------------------------------------------------
@@ -11,8 +13,8 @@
 // kernel sweeps a diagonal half column by column straight from HBM: nb dependent round trips.
 //  * gather: the block's entries flat over the workgroup (coalesced loads, the column of an entry by bisection in an LDS copy of the
 //    column pointers), products accumulated in LDS (ds_add_f64), ONE global atomic per touched row of the segment at the end;
-//  * level: the diagonal half streams through LDS in chunks of `ch` columns (rows for the upper sweep), double-buffered: three
-//    wavefronts fetch chunk k + 1 while the first one sweeps chunk k out of LDS -- a dependent step costs LDS round trips, not HBM ones.
+//  * level: the diagonal half streams through LDS in chunks of `ch` records, double-buffered: three wavefronts fetch chunk k + 1
+//    while the first one sweeps chunk k out of LDS -- a dependent step costs LDS round trips, not HBM ones.
 //
 // A sweep is an HBM stream of the factor records plus two launches per level; neither depends on how many vectors ride along.
 // Every factor entry is read once and applied to W values.
@@ -24,8 +26,54 @@
 //
 // Same per-block arithmetic as the column-by-column kernels: spmv, unit-lower column sweep, upper row sweep with the
 // PANGULU_SPTRSV_TOL clamp (real part only for complex); sums across blocks arrive in a different order.
+//
+// The four sweeps.  A x = b is a forward sweep with L, then a backward one with U; A^T = U^T L^T is a forward sweep with U^T, then a
+// backward one with L^T, on the same records read "the other way round".  The lower half of a diagonal block is strictly-lower CSC,
+// unit diagonal, colptr[0] read as 0; the upper half is CSR with the diagonal first.  Record c of either half is walked in one of two
+// ways, and the level kernel is those two steps times "does the record carry its diagonal first":
+//
+//   sweep        records      step                                                        diagonal in record
+//   SOLVE_LOWER  ascending    scatter: x[idx[p]] -= op(val[p]) x[c]                       no  (unit)
+//   SOLVE_UT     ascending    scatter, after x[c] /= op(d_c)                              yes
+//   SOLVE_UPPER  descending   dot:     x[c] = (x[c] - sum_p op(val[p]) x[idx[p]]) / d_c   yes
+//   SOLVE_LT     descending   dot:     x[c] -= sum_p op(val[p]) x[idx[p]]                 no  (unit)
+//
+// A scatter goes into distinct rows: plain LDS read-modify-write.  A dot is a lane-group partial sum per right-hand side with a
+// shuffle reduction.  d_c is divided by under the PANGULU_SPTRSV_TOL clamp (solve_clamped_divisor); an empty record is skipped, and
+// x[c] stays.  op() conjugates for A^H (CONJ: the transposed sweeps of complex builds only).
+//
+// The transposed gather: segment i receives -op(B)^T x_k from the block B = A(k, i) of its own block COLUMN.  B is stored CSC, so the
+// entries that add into one destination value are the contiguous entries of one column: a dot product, not a scatter.  Swapping row
+// and column in the flat loop of block_trsm_gather_multi_kernel would send the LDS atomics of a wavefront step to the same word.
+// There LANE GROUPS OWN COLUMNS: a group of g entry slots x W lanes walks one column, sums by shuffle and issues the column's one
+// global atomic per right-hand side; no LDS atomics, no accumulator tile, no bisection.  g is the power of two next above the block's
+// mean column length (uniform per workgroup), so that short columns of a sparse block do not idle a whole wavefront; neighbouring
+// groups take neighbouring columns, which keeps a wavefront's loads on one contiguous stretch of the record.  It needs one tile and
+// the column pointers, less than solve_multi_lds_gather: solve_widest_panel() holds for both directions.
 // -----------------------------------------------------------------------------------------------------------------
 __host__ __device__ constexpr int solve_multi_pitch(int w) { return w > 1 ? w + 1 : 1; }
+
+// What a sweep does with its records (the table above).  A run-time mode is one of the four sweeps, plus SOLVE_CONJ for A^H.
+enum
+{
+    SOLVE_LOWER = 0,
+    SOLVE_UPPER = 1,
+    SOLVE_UT = 2,
+    SOLVE_LT = 3,
+    SOLVE_CONJ = 4
+};
+__host__ __device__ constexpr bool solve_sweep_dot(int sweep) { return sweep == SOLVE_UPPER || sweep == SOLVE_LT; }        // dot step, records descending
+__host__ __device__ constexpr bool solve_sweep_diag_first(int sweep) { return sweep == SOLVE_UPPER || sweep == SOLVE_UT; } // the upper halves
+__host__ __device__ constexpr bool solve_sweep_transposed(int sweep) { return sweep == SOLVE_UT || sweep == SOLVE_LT; }
+
+template <bool CONJ>
+__host__ __device__ inline val_t solve_trans_op(val_t v)
+{
+    if constexpr (CONJ)
+        return v_conj(v);
+    else
+        return v;
+}
 
 // X_row -= A(row, j) X_j for every off-diagonal block of the level: one workgroup per block, the block's entries flat over the
 // workgroup as 256 / W entry slots x W lanes, products accumulated in an LDS tile, one global atomic per touched (row, r)
@@ -81,12 +129,109 @@ __global__ __launch_bounds__(256) void block_trsm_gather_multi_kernel(const Solv
     }
 }
 
-// The diagonal halves of the level's block rows: one workgroup per row, the nb x W segment in LDS, the diagonal half streamed
-// through LDS in double-buffered chunks of `ch` columns (rows for the upper sweep) -- three wavefronts fetch chunk k + 1 while
-// the first one sweeps chunk k.  A wavefront step is 64 / W entries x W right-hand sides.
-template <bool UPPER, int W>
-__global__ __launch_bounds__(256) void block_trsm_level_multi_kernel(const SolveRowD *__restrict__ rows, int nb, val_t *__restrict__ x, int ch)
+// entry slots per column group for a block with nnz entries: the power of two next above nnz / nb, between 1 and 64 / W
+__host__ __device__ inline int solve_trans_group_slots(u32 nnz, int nb, int w)
 {
+    const u32 mean = (nnz + (u32)nb - 1) / (u32)nb;
+    int g = 1;
+    while (g < 64 / w && (u32)g < mean)
+        g <<= 1;
+    return g;
+}
+
+// X_dst -= op(B)^T X_src for every off-diagonal block of the level: one workgroup per block (B.bcol: the source segment = the
+// block's own block row; B.brow: the destination segment = its block column), the source segment in LDS
+template <int W, bool CONJ>
+__global__ __launch_bounds__(256) void block_trsm_gather_trans_kernel(const SolveBlkD *__restrict__ blks, int nb, val_t *__restrict__ x)
+{
+    constexpr int P = solve_multi_pitch(W);
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    val_t *xs = reinterpret_cast<val_t *>(smem_raw);
+    u32 *cp = reinterpret_cast<u32 *>(xs + (size_t)nb * P);
+    const SolveBlkD B = blks[blockIdx.x];
+    const val_t *xsrc = x + (size_t)B.bcol * nb * W;
+    val_t *xdst = x + (size_t)B.brow * nb * W;
+    const int tid = threadIdx.x;
+    for (int k = tid; k < nb * W; k += 256)
+        xs[(k / W) * P + k % W] = xsrc[k];
+    for (int i = tid; i <= nb; i += 256)
+        cp[i] = i == 0 ? 0u : B.cp[i];
+    __syncthreads();
+    const int g = solve_trans_group_slots(cp[nb], nb, W); // uniform over the workgroup
+    const int span = g * W, ngroup = 256 / span;
+    const int group = tid / span, slot = (tid % span) / W, r = tid % W;
+    for (int c0 = 0; c0 < nb; c0 += ngroup) // (uniform trip count: the shuffles below are executed by whole wavefronts)
+    {
+        const int c = c0 + group;
+        val_t part = v_make(0);
+        u32 p0 = 0, p1 = 0;
+        if (c < nb)
+        {
+            p0 = cp[c];
+            p1 = cp[c + 1];
+        }
+        for (u32 p = p0 + (u32)slot; p < p1; p += (u32)g)
+            part = v_add(part, v_mul(solve_trans_op<CONJ>(B.val[p]), xs[B.ri[p] * P + r]));
+        part = solve_group_sum<W>(part, span);
+        if (slot == 0 && p0 != p1)
+            v_atomic_add(&xdst[c * W + r], v_sub(v_make(0), part));
+    }
+}
+
+// One record of a diagonal half out of its chunk in LDS (the table above), by the sweeping wavefront: record c is bv / bi[ptr[c] - base
+// .. ptr[c + 1] - base), lane = entry slot `eslot` x right-hand side `r`.  (A function of values, not a lambda over the kernel's
+// locals: the compiler then keeps what does not depend on c out of the record loop, as it did in a loop written out per sweep.)
+template <int SWEEP, int W, bool CONJ>
+__device__ inline void solve_level_step(int c, const u32 *ptr, u32 base, const val_t *bv, const u16 *bi, val_t *seg, int lane, int eslot, int r)
+{
+    constexpr bool DOT = solve_sweep_dot(SWEEP), DIAG = solve_sweep_diag_first(SWEEP);
+    constexpr int P = solve_multi_pitch(W);
+    const u32 b = ptr[c] - base, e = ptr[c + 1] - base;
+    if (b == e)
+        return;
+    const u32 first = b + (DIAG ? 1 : 0) + eslot; // this lane's first entry past the diagonal
+    if constexpr (!DOT)
+    {
+        if constexpr (DIAG)
+        {
+            if (lane < W)
+                seg[c * P + lane] = v_div(seg[c * P + lane], solve_clamped_divisor(solve_trans_op<CONJ>(bv[b])));
+            wave_lds_fence();
+        }
+        const val_t xc = seg[c * P + r];
+        for (u32 p = first; p < e; p += 64 / W)
+        {
+            val_t *d = &seg[bi[p] * P + r];
+            *d = v_submul(*d, solve_trans_op<CONJ>(bv[p]), xc);
+        }
+    }
+    else
+    {
+        // each lane group accumulates its partial dot for its right-hand side; lanes 0 .. W - 1 end up with the sums
+        val_t part = v_make(0);
+        for (u32 p = first; p < e; p += 64 / W)
+            part = v_add(part, v_mul(solve_trans_op<CONJ>(bv[p]), seg[bi[p] * P + r]));
+        part = solve_group_sum<W>(part, 64);
+        if (lane < W)
+        {
+            const val_t num = v_sub(seg[c * P + lane], part);
+            if constexpr (DIAG)
+                seg[c * P + lane] = v_div(num, solve_clamped_divisor(solve_trans_op<CONJ>(bv[b])));
+            else
+                seg[c * P + lane] = num;
+        }
+    }
+    wave_lds_fence();
+}
+
+// The diagonal halves of the level's segments, any of the four sweeps: one workgroup per segment, the nb x W segment in LDS, the
+// diagonal half streamed through LDS in double-buffered chunks of `ch` records -- three wavefronts fetch chunk k + 1 while the
+// first one sweeps chunk k.  A wavefront step is 64 / W entries x W right-hand sides.
+template <int SWEEP, int W, bool CONJ>
+__global__ __launch_bounds__(256) void block_trsm_level_kernel(const SolveRowD *__restrict__ rows, int nb, val_t *__restrict__ x, int ch)
+{
+    static_assert(!CONJ || solve_sweep_transposed(SWEEP), "only the transposed sweeps conjugate");
+    constexpr bool DOT = solve_sweep_dot(SWEEP), DIAG = solve_sweep_diag_first(SWEEP);
     constexpr int P = solve_multi_pitch(W);
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const size_t cap = (size_t)ch * (size_t)nb; // entries a chunk can hold
@@ -100,12 +245,12 @@ __global__ __launch_bounds__(256) void block_trsm_level_multi_kernel(const Solve
     for (int k = tid; k < nb * W; k += 256)
         seg[(k / W) * P + k % W] = xr[k];
     for (int i = tid; i <= nb; i += 256)
-        ptr[i] = (!UPPER && i == 0) ? 0u : R.dptr[i];
+        ptr[i] = (!DIAG && i == 0) ? 0u : R.dptr[i];
     __syncthreads();
     const int nchunk = (nb + ch - 1) / ch;
-    // chunk k: columns [k ch, (k + 1) ch) of the lower half in ascending order; rows [nb - (k + 1) ch, nb - k ch) of the upper half, descending
-    auto lo_of = [&](int k) -> int { return UPPER ? max(0, nb - (k + 1) * ch) : k * ch; };
-    auto hi_of = [&](int k) -> int { return UPPER ? nb - k * ch : min(nb, (k + 1) * ch); };
+    // chunk k: records [k ch, (k + 1) ch) in ascending order for the scatters; records [nb - (k + 1) ch, nb - k ch), descending, for the dots
+    auto lo_of = [&](int k) -> int { return DOT ? max(0, nb - (k + 1) * ch) : k * ch; };
+    auto hi_of = [&](int k) -> int { return DOT ? nb - k * ch : min(nb, (k + 1) * ch); };
     auto fetch = [&](int k, int first, int nthr)
     {
         val_t *bv = (k & 1) ? bv1 : bv0;
@@ -133,61 +278,12 @@ __global__ __launch_bounds__(256) void block_trsm_level_multi_kernel(const Solve
             const u16 *bi = (k & 1) ? bi1 : bi0;
             const int c0 = lo_of(k), c1 = hi_of(k);
             const u32 base = ptr[c0];
-            if (!UPPER)
-            {
-                for (int c = c0; c < c1; c++)
-                {
-                    const u32 p0 = ptr[c] - base, p1 = ptr[c + 1] - base;
-                    if (p0 == p1)
-                        continue;
-                    const val_t xc = seg[c * P + r];
-                    for (u32 p = p0 + eslot; p < p1; p += 64 / W)
-                    {
-                        val_t *d = &seg[bi[p] * P + r];
-                        *d = v_submul(*d, bv[p], xc);
-                    }
-                    wave_lds_fence();
-                }
-            }
+            if constexpr (DOT)
+                for (int c = c1 - 1; c >= c0; c--)
+                    solve_level_step<SWEEP, W, CONJ>(c, ptr, base, bv, bi, seg, lane, eslot, r);
             else
-            {
-                for (int row = c1 - 1; row >= c0; row--)
-                {
-                    const u32 b = ptr[row] - base, e = ptr[row + 1] - base;
-                    if (b == e)
-                        continue;
-                    // each lane group accumulates its partial dot for its right-hand side; lanes 0 .. W - 1 end up with the sums
-#ifdef PANGULU_COMPLEX
-                    val_t part = v_make(0);
-                    for (u32 p = b + 1 + eslot; p < e; p += 64 / W)
-                    {
-                        const val_t m = v_mul(bv[p], seg[bi[p] * P + r]);
-                        part.re += m.re;
-                        part.im += m.im;
-                    }
-                    for (int off = 32; off >= W; off >>= 1)
-                    {
-                        part.re += __shfl_down(part.re, off, 64);
-                        part.im += __shfl_down(part.im, off, 64);
-                    }
-#else
-                    val_t part = 0;
-                    for (u32 p = b + 1 + eslot; p < e; p += 64 / W)
-                        part += bv[p] * seg[bi[p] * P + r];
-                    for (int off = 32; off >= W; off >>= 1)
-                        part += __shfl_down(part, off, 64);
-#endif
-                    if (lane < W)
-                    {
-                        val_t d = bv[b];
-                        const real_t dr = v_realpart(d);
-                        if (!((dr < 0 ? -dr : dr) > (real_t)PANGULU_SPTRSV_TOL))
-                            d = v_make((real_t)PANGULU_SPTRSV_TOL);
-                        seg[row * P + lane] = v_div(v_sub(seg[row * P + lane], part), d);
-                    }
-                    wave_lds_fence();
-                }
-            }
+                for (int c = c0; c < c1; c++)
+                    solve_level_step<SWEEP, W, CONJ>(c, ptr, base, bv, bi, seg, lane, eslot, r);
         }
         __syncthreads();
     }
@@ -195,11 +291,15 @@ __global__ __launch_bounds__(256) void block_trsm_level_multi_kernel(const Solve
         xr[k] = seg[(k / W) * P + k % W];
 }
 
-// LDS demand of the two kernels for a panel of w right-hand sides, and the chunk depth the level kernel gets out of `budget` bytes
-// (at most 16 columns; 0: not even one fits beside the segment)
+// LDS demand of the kernels for a panel of w right-hand sides (the transposed gather: never more than solve_multi_lds_gather), and
+// the chunk depth the level kernel gets out of `budget` bytes (at most 16 records; 0: not even one fits beside the segment)
 inline size_t solve_multi_lds_gather(size_t nb, int w)
 {
     return 2 * sizeof(val_t) * nb * (size_t)solve_multi_pitch(w) + sizeof(u32) * (nb + 1) + sizeof(u32) * nb;
+}
+inline size_t solve_trans_lds_gather(size_t nb, int w)
+{
+    return sizeof(val_t) * nb * (size_t)solve_multi_pitch(w) + sizeof(u32) * (nb + 1);
 }
 inline int solve_multi_chunk(size_t nb, int w, size_t budget)
 {

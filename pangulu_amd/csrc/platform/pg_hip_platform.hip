@@ -75,6 +75,7 @@ extern "C"
 #ifdef PANGULU_COMPLEX
 __host__ __device__ inline val_t v_make(real_t r) { return val_t{r, (real_t)0}; }
 __host__ __device__ inline val_t v_mul(val_t a, val_t b) { return val_t{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+__host__ __device__ inline val_t v_add(val_t a, val_t b) { return val_t{a.re + b.re, a.im + b.im}; }
 __host__ __device__ inline val_t v_sub(val_t a, val_t b) { return val_t{a.re - b.re, a.im - b.im}; }
 // a - b*c
 __host__ __device__ inline val_t v_submul(val_t a, val_t b, val_t c)
@@ -91,6 +92,7 @@ __host__ __device__ inline val_t v_conj(val_t a) { return val_t{a.re, -a.im}; }
 #else
 __host__ __device__ inline val_t v_make(real_t r) { return r; }
 __host__ __device__ inline val_t v_mul(val_t a, val_t b) { return a * b; }
+__host__ __device__ inline val_t v_add(val_t a, val_t b) { return a + b; }
 __host__ __device__ inline val_t v_sub(val_t a, val_t b) { return a - b; }
 __host__ __device__ inline val_t v_submul(val_t a, val_t b, val_t c) { return a - b * c; } // contracts to one FMA
 __host__ __device__ inline val_t v_div(val_t a, val_t b) { return a / b; }
@@ -793,6 +795,7 @@ __global__ void getrf_flop_count_kernel(const GetrfTaskD *__restrict__ tasks, in
 }
 #endif
 
+#include "pg_hip_solve_arith.h"
 #include "pg_hip_solve_ops.h"
 
 // =================================================================================================================
@@ -803,21 +806,12 @@ namespace
 
 #include "pg_hip_block_solve.h"
 #include "pg_hip_block_solve_multi.h"
-#include "pg_hip_block_solve_trans.h"
 
 #include "pg_hip_backend.h"
 
-// What a sweep does with its records: L (unit, forward), U (backward), or -- the transposed solve, pg_hip_block_solve_trans.h --
-// U^T (forward, on the upper halves) and L^T (backward, on the lower halves), with SOLVE_CONJ added for A^H.
-enum
-{
-    SOLVE_LOWER = 0,
-    SOLVE_UPPER = 1,
-    SOLVE_UT = 2,
-    SOLVE_LT = 3,
-    SOLVE_CONJ = 4
-};
-inline bool solve_mode_upper_half(int mode) { return (mode & 3) == SOLVE_UPPER || (mode & 3) == SOLVE_UT; }
+// A sweep's run-time mode (pg_hip_block_solve_multi.h): SOLVE_LOWER / SOLVE_UPPER, or SOLVE_UT / SOLVE_LT with SOLVE_CONJ added for A^H
+inline int solve_mode_sweep(int mode) { return mode & 3; }
+inline bool solve_mode_upper_half(int mode) { return solve_sweep_diag_first(solve_mode_sweep(mode)); }
 
 // device-side descriptors of one sweep, appended to hr / hb: rows keep their order, the blocks of level l are
 // hb[blk_level_ptr[l] .. blk_level_ptr[l + 1]) counted from the first block appended here.  `mode`: see above (a transposed
@@ -880,36 +874,80 @@ int solve_widest_panel(size_t nb)
 // what one sweep of a solve call has on the device: its rows and blocks start at row0 / blk0 of the call's descriptor arrays
 struct SolveSweepD
 {
-    int upper; // SOLVE_LOWER / SOLVE_UPPER, or a transposed mode
+    int mode; // SOLVE_LOWER / SOLVE_UPPER, or a transposed mode
     const pangulu_hip_solve_sweep_t *sw;
     size_t row0, blk0;
     std::vector<size_t> blk_level_ptr;
 };
 
-// one level of a transposed sweep: the gather over the level's blocks, then its diagonal halves.  Every instantiation keeps its own
-// record of the dynamic LDS it has been allowed.
-template <int W, bool CONJ>
-void launch_solve_trans_level(bool lt, int nb, int ch, size_t nbl, size_t n, const SolveBlkD *blks, const SolveRowD *rows, val_t *d_x)
+// lets one kernel instantiation ask for `lds` bytes of dynamic LDS; each instantiation remembers the most it has been granted
+template <auto KERNEL>
+void solve_allow_lds(size_t lds)
 {
-    const size_t lds_gather = solve_trans_lds_gather((size_t)nb, W), lds_level = solve_multi_lds_level((size_t)nb, W, ch);
-    static size_t allowed_gather = 0, allowed_level = 0;
-    if (lds_gather > allowed_gather)
+    static size_t allowed = 0;
+    if (lds > allowed)
     {
-        HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_gather_trans_kernel<W, CONJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gather));
-        allowed_gather = lds_gather;
+        HIP_CHECK(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        allowed = lds;
     }
-    if (lds_level > allowed_level)
+}
+
+// one level of one sweep on a panel of W right-hand sides: the gather over the level's nbl blocks, then the diagonal halves of its n segments
+template <int SWEEP, int W, bool CONJ>
+void launch_solve_level_as(int nb, int ch, size_t nbl, size_t n, const SolveBlkD *blks, const SolveRowD *rows, val_t *d_x)
+{
+    const size_t lds_level = solve_multi_lds_level((size_t)nb, W, ch);
+    if constexpr (solve_sweep_transposed(SWEEP))
     {
-        HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_trans_kernel<false, W, CONJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
-        HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_trans_kernel<true, W, CONJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
-        allowed_level = lds_level;
+        const size_t lds_gather = solve_trans_lds_gather((size_t)nb, W);
+        solve_allow_lds<block_trsm_gather_trans_kernel<W, CONJ>>(lds_gather);
+        if (nbl)
+            hipLaunchKernelGGL((block_trsm_gather_trans_kernel<W, CONJ>), dim3((unsigned)nbl), dim3(256), lds_gather, B.stream, blks, nb, d_x);
     }
-    if (nbl)
-        hipLaunchKernelGGL((block_trsm_gather_trans_kernel<W, CONJ>), dim3((unsigned)nbl), dim3(256), lds_gather, B.stream, blks, nb, d_x);
-    if (lt)
-        hipLaunchKernelGGL((block_trsm_level_trans_kernel<true, W, CONJ>), dim3((unsigned)n), dim3(256), lds_level, B.stream, rows, nb, d_x, ch);
     else
-        hipLaunchKernelGGL((block_trsm_level_trans_kernel<false, W, CONJ>), dim3((unsigned)n), dim3(256), lds_level, B.stream, rows, nb, d_x, ch);
+    {
+        const size_t lds_gather = solve_multi_lds_gather((size_t)nb, W);
+        solve_allow_lds<block_trsm_gather_multi_kernel<W>>(lds_gather);
+        if (nbl)
+            hipLaunchKernelGGL(block_trsm_gather_multi_kernel<W>, dim3((unsigned)nbl), dim3(256), lds_gather, B.stream, blks, nb, d_x);
+    }
+    solve_allow_lds<block_trsm_level_kernel<SWEEP, W, CONJ>>(lds_level);
+    hipLaunchKernelGGL((block_trsm_level_kernel<SWEEP, W, CONJ>), dim3((unsigned)n), dim3(256), lds_level, B.stream, rows, nb, d_x, ch);
+}
+
+// the same for a run-time mode.  by_column: the column-by-column pair of pg_hip_block_solve.h (single vectors, untransposed sweeps: the
+// operator offers no transposed sweep where that pair would run)
+template <int W>
+void launch_solve_level(int mode, bool by_column, int nb, int ch, size_t nbl, size_t n, const SolveBlkD *blks, const SolveRowD *rows, val_t *d_x)
+{
+    if (by_column)
+    {
+        const size_t lds = sizeof(val_t) * (size_t)nb;
+        if (nbl)
+            hipLaunchKernelGGL(block_trsv_gather_kernel, dim3((unsigned)nbl), dim3(256), 0, B.stream, blks, nb, d_x);
+        if (solve_mode_sweep(mode) == SOLVE_UPPER)
+            hipLaunchKernelGGL(block_trsv_level_kernel<true>, dim3((unsigned)n), dim3(64), lds, B.stream, rows, nb, d_x);
+        else
+            hipLaunchKernelGGL(block_trsv_level_kernel<false>, dim3((unsigned)n), dim3(64), lds, B.stream, rows, nb, d_x);
+        return;
+    }
+    switch (mode)
+    {
+    case SOLVE_LOWER:
+        return launch_solve_level_as<SOLVE_LOWER, W, false>(nb, ch, nbl, n, blks, rows, d_x);
+    case SOLVE_UPPER:
+        return launch_solve_level_as<SOLVE_UPPER, W, false>(nb, ch, nbl, n, blks, rows, d_x);
+    case SOLVE_UT:
+        return launch_solve_level_as<SOLVE_UT, W, false>(nb, ch, nbl, n, blks, rows, d_x);
+    case SOLVE_LT:
+        return launch_solve_level_as<SOLVE_LT, W, false>(nb, ch, nbl, n, blks, rows, d_x);
+#ifdef PANGULU_COMPLEX // (real builds: A^H is A^T, the operator never adds SOLVE_CONJ)
+    case SOLVE_UT | SOLVE_CONJ:
+        return launch_solve_level_as<SOLVE_UT, W, true>(nb, ch, nbl, n, blks, rows, d_x);
+    case SOLVE_LT | SOLVE_CONJ:
+        return launch_solve_level_as<SOLVE_LT, W, true>(nb, ch, nbl, n, blks, rows, d_x);
+#endif
+    }
 }
 
 // the launches of one panel of W right-hand sides in d_x: the sweeps one after the other, a gather and a level launch per level
@@ -918,22 +956,6 @@ void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, const So
 {
     const bool by_column = W == 1 && solve_by_column((size_t)nb);
     const int ch = by_column ? 0 : solve_multi_chunk((size_t)nb, W, SOLVE_LDS_BUDGET);
-    const size_t lds_gather = solve_multi_lds_gather((size_t)nb, W), lds_level = solve_multi_lds_level((size_t)nb, W, ch);
-    if (!by_column)
-    {
-        static size_t allowed_gather = 0, allowed_level = 0; // (per W: one instantiation per width)
-        if (lds_gather > allowed_gather)
-        {
-            HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_gather_multi_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gather));
-            allowed_gather = lds_gather;
-        }
-        if (lds_level > allowed_level)
-        {
-            HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_multi_kernel<false, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
-            HIP_CHECK(hipFuncSetAttribute((const void *)block_trsm_level_multi_kernel<true, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_level));
-            allowed_level = lds_level;
-        }
-    }
     for (const SolveSweepD &S : sweeps)
         for (size_t l = 0; l < (size_t)S.sw->nlevel; l++)
         {
@@ -943,40 +965,14 @@ void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, const So
                 continue;
             const SolveBlkD *blks = d_blks + S.blk0 + S.blk_level_ptr[l];
             const SolveRowD *rows = d_rows + S.row0 + lp[l];
-            if ((S.upper & 3) >= SOLVE_UT) // (the operator offers no transposed sweep where the column-by-column pair would run)
-            {
-#ifdef PANGULU_COMPLEX
-                if (S.upper & SOLVE_CONJ)
-                    launch_solve_trans_level<W, true>((S.upper & 3) == SOLVE_LT, nb, ch, nbl, n, blks, rows, d_x);
-                else
-#endif
-                    launch_solve_trans_level<W, false>((S.upper & 3) == SOLVE_LT, nb, ch, nbl, n, blks, rows, d_x);
-                continue;
-            }
-            if (by_column)
-            {
-                const size_t lds = sizeof(val_t) * (size_t)nb;
-                if (nbl)
-                    hipLaunchKernelGGL(block_trsv_gather_kernel, dim3((unsigned)nbl), dim3(256), 0, B.stream, blks, nb, d_x);
-                if (S.upper)
-                    hipLaunchKernelGGL(block_trsv_level_kernel<true>, dim3((unsigned)n), dim3(64), lds, B.stream, rows, nb, d_x);
-                else
-                    hipLaunchKernelGGL(block_trsv_level_kernel<false>, dim3((unsigned)n), dim3(64), lds, B.stream, rows, nb, d_x);
-                continue;
-            }
-            if (nbl)
-                hipLaunchKernelGGL(block_trsm_gather_multi_kernel<W>, dim3((unsigned)nbl), dim3(256), lds_gather, B.stream, blks, nb, d_x);
-            if (S.upper)
-                hipLaunchKernelGGL((block_trsm_level_multi_kernel<true, W>), dim3((unsigned)n), dim3(256), lds_level, B.stream, rows, nb, d_x, ch);
-            else
-                hipLaunchKernelGGL((block_trsm_level_multi_kernel<false, W>), dim3((unsigned)n), dim3(256), lds_level, B.stream, rows, nb, d_x, ch);
+            launch_solve_level<W>(S.mode, by_column, nb, ch, nbl, n, blks, rows, d_x);
         }
 }
 
 // The level-scheduled block triangular solve, both operators' body: the descriptors of the given sweeps (one, or the lower and then
 // the upper one; or U^T and then L^T) go up once; the panels of the HOST buffer X (panel p: xlen x w[p] values, right-hand side fastest, w[p] a width
 // solve_widest_panel() allows) then pass through one device buffer one after the other: upload, the sweeps, download.
-void block_solve_panels(int nb, const std::vector<const pangulu_hip_solve_sweep_t *> &sw, const std::vector<int> &upper, val_t *X, size_t xlen, size_t npanel,
+void block_solve_panels(int nb, const std::vector<const pangulu_hip_solve_sweep_t *> &sw, const std::vector<int> &mode, val_t *X, size_t xlen, size_t npanel,
                         const int *w)
 {
     ensure_ready();
@@ -990,11 +986,11 @@ void block_solve_panels(int nb, const std::vector<const pangulu_hip_solve_sweep_
     std::vector<SolveSweepD> sweeps(sw.size());
     for (size_t s = 0; s < sw.size(); s++)
     {
-        sweeps[s].upper = upper[s];
+        sweeps[s].mode = mode[s];
         sweeps[s].sw = sw[s];
         sweeps[s].row0 = hr.size();
         sweeps[s].blk0 = hb.size();
-        append_solve_descriptors(upper[s], *sw[s], hr, hb, sweeps[s].blk_level_ptr);
+        append_solve_descriptors(mode[s], *sw[s], hr, hb, sweeps[s].blk_level_ptr);
     }
     if (hr.empty())
         hr.resize(1);
@@ -1749,7 +1745,7 @@ extern "C"
     {
         const pangulu_hip_solve_sweep_t sw = {nlevel, level_ptr, rows, blk_slots, blk_bcol};
         const int one = 1;
-        block_solve_panels((int)nb, {&sw}, {upper ? 1 : 0}, x, (size_t)xlen, 1, &one);
+        block_solve_panels((int)nb, {&sw}, {upper ? SOLVE_UPPER : SOLVE_LOWER}, x, (size_t)xlen, 1, &one);
     }
 
     // Both sweeps for panels of right-hand sides: the descriptors of both sweeps go up once and serve all the panels.
@@ -1765,11 +1761,11 @@ extern "C"
                 fprintf(stderr, "[PanguLU-AMD ERROR] block_trsm_multi: panel width %d (nb = %d takes powers of two up to %d)\n", w[p], (int)nb, wmax);
                 exit(EXIT_FAILURE);
             }
-        block_solve_panels((int)nb, {lower, upper}, {0, 1}, X, (size_t)xlen, (size_t)npanel, w);
+        block_solve_panels((int)nb, {lower, upper}, {SOLVE_LOWER, SOLVE_UPPER}, X, (size_t)xlen, (size_t)npanel, w);
         return wmax;
     }
 
-    // The transposed solve: a forward sweep with U^T, then a backward sweep with L^T (pg_hip_block_solve_trans.h), through the same
+    // The transposed solve: a forward sweep with U^T, then a backward sweep with L^T (pg_hip_block_solve_multi.h), through the same
     // launch routine.  0: no transposed kernels here (the column-by-column pair has no transposed twin).
     int pangulu_platform_0201001_block_trsm_multi_trans(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *forward_ut,
                                                         const pangulu_hip_solve_sweep_t *backward_lt, int conjugate, calculate_type *X,

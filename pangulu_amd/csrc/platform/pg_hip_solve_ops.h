@@ -22,14 +22,7 @@ __global__ void vecadd_kernel(long long n, val_t *b, const val_t *x)
 {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n)
-    {
-#ifdef PANGULU_COMPLEX
-        b[i].re += x[i].re;
-        b[i].im += x[i].im;
-#else
-        b[i] += x[i];
-#endif
-    }
+        b[i] = v_add(b[i], x[i]);
 }
 
 __global__ void sptrsv_kernel(int nb, const u32 *ptr, const u16 *idx, const val_t *val, val_t *x, int upper)
@@ -59,33 +52,12 @@ __global__ void sptrsv_kernel(int nb, const u32 *ptr, const u16 *idx, const val_
                 continue;
             if (threadIdx.x < 64)
             {
-#ifdef PANGULU_COMPLEX
                 val_t part = v_make(0);
                 for (u32 p = b + 1 + threadIdx.x; p < e; p += 64)
-                {
-                    val_t m = v_mul(val[p], xs[idx[p]]);
-                    part.re += m.re;
-                    part.im += m.im;
-                }
-                for (int off = 32; off > 0; off >>= 1)
-                {
-                    part.re += __shfl_down(part.re, off, 64);
-                    part.im += __shfl_down(part.im, off, 64);
-                }
-#else
-                val_t part = 0;
-                for (u32 p = b + 1 + threadIdx.x; p < e; p += 64)
-                    part += val[p] * xs[idx[p]];
-                for (int off = 32; off > 0; off >>= 1)
-                    part += __shfl_down(part, off, 64);
-#endif
+                    part = v_add(part, v_mul(val[p], xs[idx[p]]));
+                part = solve_group_sum<1>(part, 64);
                 if (threadIdx.x == 0)
-                {
-                    val_t d = val[b];
-                    real_t dr = v_realpart(d);
-                    val_t num = v_sub(xs[r], part);
-                    xs[r] = ((dr < 0 ? -dr : dr) > (real_t)PANGULU_SPTRSV_TOL) ? v_div(num, d) : v_div(num, v_make((real_t)PANGULU_SPTRSV_TOL));
-                }
+                    xs[r] = v_div(v_sub(xs[r], part), solve_clamped_divisor(val[b]));
             }
             __syncthreads();
         }

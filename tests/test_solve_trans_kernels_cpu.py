@@ -1,4 +1,4 @@
-"""The kernels of pg_hip_block_solve_trans.h (A^T X = B, A^H X = B), compiled as host C++ behind shims for the few device intrinsics
+"""The transposed sweeps of pg_hip_block_solve_multi.h (A^T X = B, A^H X = B), compiled as host C++ behind shims for the few device intrinsics
 they use and run with one thread per work-item (tests/solve_trans_kernel_emulation.cpp), against dense substitution with U^T / L^T
 (U^H / L^H): every panel width, both sweeps, real and complex values, conjugation on and off, block orders that are a multiple of
 nothing, several chunks per diagonal half, an empty row record and a row of U whose only entry is a diagonal below the clamp.  A

@@ -14,7 +14,8 @@ t0 = int(s[0]['Start_Timestamp'])
 print("factorisations", [len(x) for x in segs], "last: %.2f ms" % ((max(int(r['End_Timestamp']) for r in s) - t0) / 1e6))
 short = {'ssssm_dense_f64_kernel': 'SD', 'void ssssm_sparse_kernel<false>': 'SS', 'void trsm_dense_f64_kernel<16>': 'TD', 'trsm_sparse_kernel': 'TS',
          'densify_kernel': 'dn', 'getrf_blocked_f64_kernel': 'G', 'sparsify_kernel': 'sp', 'diag_tile_inverse_kernel': 'di'}
-solve = ('block_trsm_gather_multi_kernel', 'block_trsm_level_multi_kernel', 'block_trsv_gather_kernel', 'block_trsv_level_kernel')  # pangulu_gstrs
+solve = ('block_trsm_gather_multi_kernel', 'block_trsm_gather_trans_kernel', 'block_trsm_level_kernel', 'block_trsv_gather_kernel',
+         'block_trsv_level_kernel')  # pangulu_gstrs, pangulu_amd_gstrs_multi / _trans
 out = []
 for r in s:
     k = r['Kernel_Name'].split('(')[0]
