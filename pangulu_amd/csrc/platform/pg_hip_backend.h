@@ -84,6 +84,7 @@ struct Backend
     // piece live: LDS stages of its operand pipeline (2, 3 or 4; 0 = off, everything through the general kernel)
     long long opt_front_stages = 2; // PANGULU_HIP_FRONT_STAGES / option 15: 1 = inside the general launch (no step list), 2..4 = own kernel
     long long opt_front_min_wgs = 2048; // PANGULU_HIP_FRONT_MIN_WGS: ... from this many qualifying workgroups in a launch on (round 3 sweep, fem27(112): 842.8 / 845.0 / 849.0 ms at 8192 / 2048 / never; round 4, with the destination preloaded: 656.9 / 655.4 / 653.6 / 659.6 ms at 8192 / 2048 / 512 / 64)
+    long long opt_ksplit = 1;       // PANGULU_HIP_KSPLIT: 1 = update launches of at most 64 workgroups are cut four ways along K (launch_ssssm); 0 = never.  A K-split group never qualifies for the dense-front kernel and every launch of a directed small case is K-split: 0 is how tests/test_gpu_front_kernel_small.py reaches that kernel
     long long opt_front_unit = 1;   // PANGULU_HIP_FRONT_UNIT: consecutive destinations of the front launch that share an XCD
     // general MFMA update kernel: 0 = round 2's (register staging, contiguous sub-tiles; pg_hip_dense.h), any other value = the
     // two-stage LDS-DMA pipeline with strided piece ownership (ssssm_tilesv_f64_kernel, pg_hip_front.h).  (The values 1, 3, 4, 5
@@ -336,6 +337,8 @@ void ensure_ready()
         B.opt_front_unit = atol(e);
     if (const char *e = getenv("PANGULU_HIP_FRONT_MIN_WGS"))
         B.opt_front_min_wgs = atol(e);
+    if (const char *e = getenv("PANGULU_HIP_KSPLIT"))
+        B.opt_ksplit = atol(e);
     if (const char *e = getenv("PANGULU_HIP_TILES_STAGES"))
         B.opt_tiles_stages = atol(e);
     if (const char *e = getenv("PANGULU_HIP_GROUP_CHUNK"))

@@ -36,18 +36,33 @@
 typedef const char __attribute__((address_space(1))) *fr_gptr;
 typedef void __attribute__((address_space(3))) *fr_lptr;
 
+// Where the DMA instructions of slab st + STAGES - 1 stand inside step st (r10a):
+//   FR_ORDER 0  right behind the barrier, before any matrix-core work of the step (the order up to round 6;
+//               -DFR_ISSUE_FIRST=1 selects it for the product kernel);
+//   FR_ORDER 1  behind the eight products of k-quarter 0: the address path works in the shadow of the matrix cores, as in
+//               ssssm_tilesv_f64_kernel below.
+// (A third order, one instruction behind the products of each k-quarter, was built and lost 2.5-6 % stand-alone:
+//  profiles/r10a_front_orders.log, tools/experiments/front_issue_spread.patch.)
+// The stage that is refilled is the one slab st - 1 was read from, and every wavefront is past it at the barrier of step st:
+// the place of the issue inside the step does not change the hazard.  Every wavefront still has issued exactly four DMA
+// instructions per slab when it reaches the next step's wait, so the counted waits hold for 2, 3 and 4 stages in every order.
+#ifndef FR_ISSUE_FIRST
+#define FR_ISSUE_FIRST 0
+#endif
+#define FR_ORDER (FR_ISSUE_FIRST ? 0 : 1)
+#ifndef FR_PRELOAD
+#define FR_PRELOAD 1
+#endif
+
+// One work item of the dense-front kernel: the tile G.tile of destination G.cdense takes the whole queue
+// [G.task_begin, G.task_end).  `lds`: STAGES * FR_STAGE_DOUBLES doubles of the workgroup (FR_THREADS threads).
 // STAGES: LDS stages of the operand pipeline.  PREFETCH: the MFMA fragments of k-quarter kq + 1 are read while the matrix
-// cores work on kq (12 more registers).  `unit`: consecutive workgroups that go to the same XCD (logical_block_id): 4 =
-// the tiles of one destination; 4 g = the tiles of g consecutive destinations, which share an operand in the scheduler's
-// release order (all updates of one finished L block, or of one finished U block, are queued in a row).
-template <int STAGES, bool PREFETCH>
-__global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front_f64_kernel(const SsssmTaskD *__restrict__ tasks, int nb, const SsssmWorkD *__restrict__ work,
-                                                                     unsigned long long *__restrict__ product_counter, unsigned unit)
+// cores work on kq (12 more registers).  ORDER: see FR_ORDER.
+template <int STAGES, bool PREFETCH, int ORDER>
+__device__ __forceinline__ void fr_front_item(double *lds, const SsssmTaskD *__restrict__ tasks, int nb, const SsssmWorkD &G,
+                                              unsigned long long *__restrict__ product_counter)
 {
-    __shared__ __align__(16) double lds[STAGES * FR_STAGE_DOUBLES];
     const int tiles = nb / FR_TILE;
-    const unsigned bid = logical_block_id(unit ? unit : (unsigned)(tiles * tiles));
-    const SsssmWorkD G = work[bid];
     const int tile = (int)G.tile;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -71,12 +86,11 @@ __global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front
     for (int par = 0; par < 2; par++)
         b_voff[par] = ((unsigned)bc * (unsigned)nb + 2u * (unsigned)(bj ^ ((4 * par + (bc >> 1)) & 7))) * 8u;
 
-    auto issue = [&](int st)
+    // the DMA instructions of slab `st`, a slab of the task whose operand mirrors are pa and pb.  Four per wave: A columns
+    // `wave`, `wave + 8`; B column groups `wave`, `wave + 8`
+    auto issue = [&](int st, fr_gptr pa, fr_gptr pb)
     {
-        // four DMA instructions per wave: A columns `wave`, `wave + 8`; B column groups `wave`, `wave + 8`
-        const int t = st >> steps_shift, k0 = (st & (steps_per_task - 1)) * FR_KS;
-        const fr_gptr pa = (fr_gptr)reinterpret_cast<const char *>(my_tasks[t].a.val);
-        const fr_gptr pb = (fr_gptr)reinterpret_cast<const char *>(my_tasks[t].b.val);
+        const int k0 = (st & (steps_per_task - 1)) * FR_KS;
         double *stage = lds + (st % STAGES) * FR_STAGE_DOUBLES;
 #pragma unroll
         for (int h = 0; h < 2; h++)
@@ -105,9 +119,6 @@ __global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front
     // has done so since round 3): the loads are older than every DMA instruction, so the first step's wait covers them, they travel
     // beside the first slab, the matrix cores compute C - sum A B and the epilogue is stores only -- a read-modify-write at the end
     // is a dependent round trip nothing hides (stand-alone: FR_PRELOAD=0 for the old epilogue).
-#ifndef FR_PRELOAD
-#define FR_PRELOAD 1
-#endif
     const bool preload = FR_PRELOAD && !G.atomic && T > 0;
     v4f64 acc[2][4]; // [ni][mi]
 #pragma unroll
@@ -125,11 +136,27 @@ __global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front
                 acc[ni][mi] = (v4f64){0.0, 0.0, 0.0, 0.0};
         }
 
-    // prologue: STAGES - 1 slabs in flight
+    // (pa_rq, pb_rq): operand mirrors of the task the NEXT request belongs to, held in scalar registers.  They change once per
+    // steps_per_task steps; the pair of the following task is loaded one step before the first request that needs it, in front
+    // of that step's wait and barrier, where the wavefront is parked anyway (r10a; up to round 6 every request began with
+    // two scalar loads from the task descriptor, behind the barrier and in front of the step's first fragment read).
+    fr_gptr pa_rq = nullptr, pb_rq = nullptr;
+    if (T > 0)
+    {
+        pa_rq = (fr_gptr)reinterpret_cast<const char *>(my_tasks[0].a.val);
+        pb_rq = (fr_gptr)reinterpret_cast<const char *>(my_tasks[0].b.val);
+    }
+#if PG_PLANES > 1
+    // (complex updates as four real products: A_im B_im ADDS to the real plane) -- the sign of the task being CONSUMED, handed
+    // over at the task's first step like the pointers at its first request
+    bool add = T > 0 && my_tasks[0].sign < 0;
+#endif
+
+    // prologue: STAGES - 1 slabs in flight (all of task 0: STAGES - 1 <= 3 < steps_per_task)
 #pragma unroll
     for (int p = 0; p < STAGES - 1; p++)
         if (p < T)
-            issue(p);
+            issue(p, pa_rq, pb_rq);
 
     // fragment addresses inside a stage (doubles): A (k, m) at k * FR_LDA + m;  B (k, n) at A_IMAGE + n * 16 + 2 (kp ^ s(n)) + (k & 1)
     const int a_frag = l4 * FR_LDA + wm + l15;
@@ -144,6 +171,21 @@ __global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front
 
     for (int st = 0; st < T; st++)
     {
+        // the request of this step is slab rq; the NEXT step's request is the first of a task when rq + 1 is a multiple of
+        // steps_per_task: its pointers are fetched here and are in flight across the wait and the barrier
+        const int rq = st + STAGES - 1;
+        fr_gptr pa_nx = pa_rq, pb_nx = pb_rq;
+        if (((rq + 1) & (steps_per_task - 1)) == 0 && rq + 1 < T)
+        {
+            const SsssmTaskD &Tn = my_tasks[(rq + 1) >> steps_shift];
+            pa_nx = (fr_gptr)reinterpret_cast<const char *>(Tn.a.val);
+            pb_nx = (fr_gptr)reinterpret_cast<const char *>(Tn.b.val);
+        }
+#if PG_PLANES > 1
+        bool add_nx = add;
+        if (((st + 1) & (steps_per_task - 1)) == 0 && st + 1 < T)
+            add_nx = my_tasks[(st + 1) >> steps_shift].sign < 0;
+#endif
         // slab st has landed: this wave's own four instructions by the counted wait, everybody else's behind the barrier
         const int ahead = min(STAGES - 2, T - 1 - st); // slabs issued after slab st that may stay in flight
         if (STAGES >= 4 && ahead >= 2)
@@ -153,13 +195,11 @@ __global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        // ... and every wave has finished reading the stage slab st - 1 was in: refill it
-        if (st + STAGES - 1 < T)
-            issue(st + STAGES - 1);
+        // ... and every wave has finished reading the stage slab st - 1 was in: it may be refilled from here on
+        const bool request = rq < T;
+        if (ORDER == 0 && request)
+            issue(rq, pa_rq, pb_rq);
         const double *sA = lds + (st % STAGES) * FR_STAGE_DOUBLES;
-#if PG_PLANES > 1
-        const bool add = my_tasks[st >> steps_shift].sign < 0; // (complex updates as four real products: A_im B_im ADDS to the real plane)
-#endif
 #if PG_PLANES > 1
 #define FR_MFMA(ni_, mi_, fb_, fa_)                                                                                        \
     if (add)                                                                                                                \
@@ -174,6 +214,10 @@ __global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front
         _Pragma("unroll") for (int mi = 0; mi < 4; mi++)(fa_)[mi] = sA[a_frag + (kq_) * 4 * FR_LDA + mi * 16]; \
         _Pragma("unroll") for (int ni = 0; ni < 2; ni++)(fb_)[ni] = sA[b_frag[ni][0] + 2 * ((2 * (kq_) + (l4 >> 1)) ^ b_frag[ni][1])]; \
     }
+        // the request behind the products of k-quarter 0
+#define FR_REQUEST_BEHIND(kq_)                   \
+    if (ORDER == 1 && (kq_) == 0 && request)     \
+        issue(rq, pa_rq, pb_rq);
         if (PREFETCH)
         {
             double fa[2][4], fb[2][2];
@@ -190,6 +234,7 @@ __global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front
                     {
                         FR_MFMA(ni, mi, fb[kq & 1][ni], fa[kq & 1][mi])
                     }
+                FR_REQUEST_BEHIND(kq)
             }
         }
         else
@@ -206,10 +251,17 @@ __global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front
                     {
                         FR_MFMA(ni, mi, fb[ni], fa[mi])
                     }
+                FR_REQUEST_BEHIND(kq)
             }
         }
+#undef FR_REQUEST_BEHIND
 #undef FR_READ
 #undef FR_MFMA
+        pa_rq = pa_nx;
+        pb_rq = pb_nx;
+#if PG_PLANES > 1
+        add = add_nx;
+#endif
     }
     if (product_counter && lane == 0 && T)
         atomicAdd(product_counter, (unsigned long long)(8 * T)); // 16 x 16 x 16 products issued by this wave
@@ -251,6 +303,20 @@ __global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front
                 FR_C(ni, mi, r) = old[mi][r] + acc[ni][mi][r];
     }
 #undef FR_C
+}
+
+// `unit`: consecutive workgroups that go to the same XCD (logical_block_id): 4 = the tiles of one destination; 4 g = the tiles
+// of g consecutive destinations, which share an operand in the scheduler's release order (all updates of one finished L block,
+// or of one finished U block, are queued in a row).
+template <int STAGES, bool PREFETCH>
+__global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void ssssm_front_f64_kernel(const SsssmTaskD *__restrict__ tasks, int nb, const SsssmWorkD *__restrict__ work,
+                                                                     unsigned long long *__restrict__ product_counter, unsigned unit)
+{
+    __shared__ __align__(16) double lds[STAGES * FR_STAGE_DOUBLES];
+    const int tiles = nb / FR_TILE;
+    const unsigned bid = logical_block_id(unit ? unit : (unsigned)(tiles * tiles));
+    const SsssmWorkD G = work[bid];
+    fr_front_item<STAGES, PREFETCH, FR_ORDER>(lds, tasks, nb, G, product_counter);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -308,6 +374,14 @@ __global__ __launch_bounds__(FR_THREADS, 4) void ssssm_tilesv_f64_kernel(const S
     const int M0 = (tile % tiles) * FR_TILE, N0 = (tile / tiles) * FR_TILE;
     const int wr = wave & 1, wc = wave >> 1; // row pieces 2 mi + wr, column pieces wc + 4 ni
     const int l15 = lane & 15, l4 = lane >> 4;
+    if (G.pad_ != 0)
+    {
+        // a dense-front pair that stays in this launch (launch_ssssm: fewer qualifying pairs in the call than a launch of their own
+        // pays for; every piece of every operand live, no K-split): the front kernel's step loop -- no step list, no tests
+        // (r10a; until then such an item walked the tested loop below over a list of all its steps).  Same stage size.
+        fr_front_item<2, true, FR_ORDER>(lds, tasks, nb, G, product_counter);
+        return;
+    }
     const int ntask = (int)(G.task_end - G.task_begin);
     const int nslab = nb / FR_KS;
     const SsssmTaskD *my_tasks = tasks + G.task_begin;
@@ -334,8 +408,6 @@ __global__ __launch_bounds__(FR_THREADS, 4) void ssssm_tilesv_f64_kernel(const S
         b_frag[ni][0] = FR_KS * FR_LDA + n * 16 + (l4 & 1);
         b_frag[ni][1] = (n >> 1) & 7;
     }
-    const bool all_live = G.pad_ != 0;
-    const int slab_shift = nb == 256 ? 4 : 3;
 
     auto uniform64 = [&](unsigned long long v) -> fr_gptr
     { return (fr_gptr)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v)); };
@@ -380,25 +452,6 @@ __global__ __launch_bounds__(FR_THREADS, 4) void ssssm_tilesv_f64_kernel(const S
         // ---- the window's step list (no DMA is in flight here: plain barriers) --------------------------------------
         __syncthreads();
         int T;
-        if (all_live)
-        {
-            // step e = slab e & (nslab - 1) of task e >> slab_shift, every piece live
-            T = min(TL_WINDOW, ntask - win0) * nslab;
-            if (tid < T)
-            {
-                const int t_ = tid >> slab_shift;
-                const SsssmTaskD &Tm = my_tasks[win0 + t_];
-                s_step[tid] = ((unsigned)t_ << 20) | ((unsigned)(tid & (nslab - 1)) << 16) | 0xFFFFu;
-                s_spa[tid] = (unsigned long long)reinterpret_cast<const double *>(Tm.a.val);
-                s_spb[tid] = (unsigned long long)reinterpret_cast<const double *>(Tm.b.val);
-#if PG_PLANES > 1
-                if ((tid & (nslab - 1)) == 0)
-                    s_sign[t_] = Tm.sign;
-#endif
-            }
-            __syncthreads();
-        }
-        else
         {
             unsigned v = 0;
             unsigned long long pa_v = 0, pb_v = 0;
@@ -461,24 +514,19 @@ __global__ __launch_bounds__(FR_THREADS, 4) void ssssm_tilesv_f64_kernel(const S
         if (may_preload)
         {
             unsigned m = 0;
-            if (all_live)
-                m = 0xFFu;
-            else
+            for (int e = lane; e < T; e += 64)
             {
-                for (int e = lane; e < T; e += 64)
-                {
-                    const unsigned w = s_step[e];
-                    const unsigned ab = w & 0xFFu, bb = (w >> 8) & 0xFFu;
-                    const unsigned a4 = ((ab >> wr) & 1u) | (((ab >> (2 + wr)) & 1u) << 1) | (((ab >> (4 + wr)) & 1u) << 2) | (((ab >> (6 + wr)) & 1u) << 3);
-                    if ((bb >> wc) & 1u)
-                        m |= a4;
-                    if ((bb >> (wc + 4)) & 1u)
-                        m |= a4 << 4;
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1)
-                    m |= (unsigned)__shfl_xor((int)m, off, 64);
+                const unsigned w = s_step[e];
+                const unsigned ab = w & 0xFFu, bb = (w >> 8) & 0xFFu;
+                const unsigned a4 = ((ab >> wr) & 1u) | (((ab >> (2 + wr)) & 1u) << 1) | (((ab >> (4 + wr)) & 1u) << 2) | (((ab >> (6 + wr)) & 1u) << 3);
+                if ((bb >> wc) & 1u)
+                    m |= a4;
+                if ((bb >> (wc + 4)) & 1u)
+                    m |= a4 << 4;
             }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1)
+                m |= (unsigned)__shfl_xor((int)m, off, 64);
             pre = (unsigned)__builtin_amdgcn_readfirstlane((int)m);
 #pragma unroll
             for (int ni = 0; ni < 2; ni++)

@@ -56,7 +56,7 @@ void launch_ssssm(int nb, task_t **list, size_t n, bool background = false)
         SsssmTaskD *tasks_s = seg.alloc<SsssmTaskD>(take, &d_tasks_s);
         SsssmTaskD *tasks_d = seg.alloc<SsssmTaskD>(take * PG_PLANES * PG_PLANES, &d_tasks_d); // (CR64: four real products per update)
         const int tiles_per_dim = nb >= DG_TILE_HOST ? nb / DG_TILE_HOST : 1;
-        const unsigned ksplit = (nb <= 256 && nb % 64 == 0 && take * (size_t)(tiles_per_dim * tiles_per_dim) <= 64) ? 4u : 1u;
+        const unsigned ksplit = (B.opt_ksplit != 0 && nb <= 256 && nb % 64 == 0 && take * (size_t)(tiles_per_dim * tiles_per_dim) <= 64) ? 4u : 1u;
         SsssmGroupD *groups_s = seg.alloc<SsssmGroupD>(take, &d_groups_s);
         SsssmGroupD *groups_d = seg.alloc<SsssmGroupD>(take * ksplit * PG_PLANES, &d_groups_d);
         static std::vector<unsigned short> live_k; // per dense task and tile: K-slabs in which both operands have entries

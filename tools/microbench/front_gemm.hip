@@ -2,7 +2,8 @@
 // ssssm_dense_f64_kernel (pg_hip_dense.h) with every tile live.  The shape of one level of a dense separator: P x P
 // destination blocks C(i,j) -= sum_q A_q(i) B_q(j), nb = 256, four 128 x 128 tiles each.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -o front_gemm.bin front_gemm.hip
-//   ./front_gemm.bin [P = 40] [Q = 1]
+//   ./front_gemm.bin [P = 40] [Q = 1] [fill = 100]
+//   ./front_gemm.bin P 0 100 orders      the two places of the DMA issue inside a front step, side by side (orders_mode)
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -56,6 +57,19 @@ __device__ unsigned long long g_sw_probe[8];
 #include "../experiments/pg_hip_stream.h"
 #include "../experiments/front_k32.h"
 #include "../experiments/front_n64.h"
+// r10a: the dense-front work item (fr_front_item, pg_hip_front.h) with the place of the DMA issue inside a step as a template
+// parameter, so that one binary checks and times both orders side by side (FR_ORDER: 0 = behind the barrier, 1 = behind
+// the first k-quarter's products; a third, one instruction behind each k-quarter's products, is tools/experiments/front_issue_spread.patch)
+template <int STAGES, int ORDER>
+__global__ __launch_bounds__(FR_THREADS, (STAGES <= 2 ? 4 : 2)) void front_order_kernel(const SsssmTaskD *__restrict__ tasks, int nb, const SsssmWorkD *__restrict__ work,
+                                                                                         unsigned long long *__restrict__ product_counter, unsigned unit)
+{
+    __shared__ __align__(16) double lds[STAGES * FR_STAGE_DOUBLES];
+    const int tiles = nb / FR_TILE;
+    const unsigned bid = logical_block_id(unit ? unit : (unsigned)(tiles * tiles));
+    const SsssmWorkD G = work[bid];
+    fr_front_item<STAGES, true, ORDER>(lds, tasks, nb, G, product_counter);
+}
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 
 struct Problem
@@ -169,7 +183,8 @@ void build(Problem &X, int P, int Q, bool keep_host, int fill = 100)
     CK(hipMalloc(&X.dSteps, sizeof(SsssmStepD) * W.size() * (size_t)Q * 16));
 }
 
-// which: 0 = general kernel; otherwise 100 * unit_destinations + 10 * prefetch + stages
+// which: 0 = general kernel; below 1000: 100 * unit_destinations + 10 * prefetch + stages (the product's front kernel);
+// 70000 + 1000 * order + 100 * unit_destinations + stages: front_order_kernel<stages, order>
 void launch(int which, Problem &X)
 {
     static const unsigned cap = getenv("GRID_CAP") ? (unsigned)atoi(getenv("GRID_CAP")) : 0u; // (timing experiments: only the first workgroups)
@@ -178,6 +193,21 @@ void launch(int which, Problem &X)
     if (which == 0)
     {
         hipLaunchKernelGGL(ssssm_dense_f64_kernel, dim3(grid), dim3(DG_THREADS), 0, 0, X.dT, X.nb, none, none, X.dW);
+        CK(hipGetLastError());
+        return;
+    }
+    if (which >= 70000)
+    {
+        const unsigned unit = 4u * (unsigned)((which / 100) % 10);
+        const int order = (which / 1000) % 10, st = which % 10;
+#define GO(S_, O_) hipLaunchKernelGGL((front_order_kernel<S_, O_>), dim3(grid), dim3(FR_THREADS), 0, 0, X.dT, X.nb, X.dW, none, unit)
+        if (st == 2 && order == 0) GO(2, 0);
+        else if (st == 2) GO(2, 1);
+        else if (st == 3 && order == 0) GO(3, 0);
+        else if (st == 3) GO(3, 1);
+        else if (order == 0) GO(4, 0);
+        else GO(4, 1);
+#undef GO
         CK(hipGetLastError());
         return;
     }
@@ -261,6 +291,12 @@ const char *name_of(int which)
 {
     if (which == 0)
         return "round-2 kernel (pg_hip_dense.h)";
+    if (which >= 70000)
+    {
+        static const char *const order_name[2] = {"behind the barrier", "behind quarter 0's products"};
+        snprintf(name_buf, sizeof(name_buf), "front kernel, %d LDS stages, DMA issue %s", which % 10, order_name[(which / 1000) % 10]);
+        return name_buf;
+    }
     if (which >= 60000)
     {
         snprintf(name_buf, sizeof(name_buf), "stream kernel (16 wavefronts, 4 stages, persistent), %d workgroups", which % 1000 ? which % 1000 : 256);
@@ -317,9 +353,89 @@ void reference(Problem &X, int i, int j, std::vector<double> &ref)
     }
 }
 
+// best and mean-of-4 time of one kind on a built problem
+static void time_kind(int which, Problem &X, float *best_ms, float *mean_ms)
+{
+    hipEvent_t a, b;
+    CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
+    float best = 1e30f, sum = 0;
+    for (int rep = 0; rep < 5; rep++)
+    {
+        CK(hipEventRecord(a));
+        launch(which, X);
+        CK(hipEventRecord(b));
+        CK(hipEventSynchronize(b));
+        float ms;
+        CK(hipEventElapsedTime(&ms, a, b));
+        best = fminf(best, ms);
+        if (rep) sum += ms;
+    }
+    CK(hipEventDestroy(a)); CK(hipEventDestroy(b));
+    *best_ms = best;
+    *mean_ms = sum / 4;
+}
+
+// `orders` mode (r10a): the two places of the DMA issue, full tiles, 1 / 2 / 4 / 8 updates per tile, 2 and 3 stages: every
+// variant is checked entry by entry against the host product on a small front with the same queue length, then timed on P x P
+// destinations -- twice, interleaved, so that a drift of the box shows as a difference between the two rounds
+static int orders_mode(int P)
+{
+    const std::vector<int> kinds = {70102, 71102, 70103, 71103};
+    bool all_ok = true;
+    for (int Q : {1, 2, 4, 8})
+    {
+        {
+            Problem X;
+            build(X, 2, Q, true, 100);
+            const int nb = X.nb;
+            std::vector<double> ref((size_t)nb * nb), got((size_t)X.mb);
+            std::vector<int> checked = kinds;
+            checked.insert(checked.end(), {70104, 71104});
+            for (int which : checked)
+            {
+                for (int i = 0; i < X.P; i++)
+                    for (int j = 0; j < X.P; j++)
+                        CK(hipMemcpy(X.C(i, j), X.h.data() + X.offC(i, j), sizeof(double) * X.mb, hipMemcpyHostToDevice));
+                launch(which, X);
+                CK(hipDeviceSynchronize());
+                double worst = 0;
+                for (int i = 0; i < X.P; i++)
+                {
+                    const int j = (i + 1) % X.P; // (two of the four destinations: every A and every B operand once)
+                    reference(X, i, j, ref);
+                    CK(hipMemcpy(got.data(), X.C(i, j), sizeof(double) * X.mb, hipMemcpyDeviceToHost));
+                    for (size_t e = 0; e < (size_t)nb * nb; e++)
+                        worst = fmax(worst, fabs(got[e] - ref[e]));
+                }
+                const bool ok = worst < 1e-11;
+                all_ok = all_ok && ok;
+                printf("check  Q = %d  %-66s max |C - ref| = %.3e %s\n", Q, name_of(which), worst, ok ? "ok" : "WRONG");
+            }
+            CK(hipFree(X.d)); CK(hipFree(X.dT)); CK(hipFree(X.dW)); CK(hipFree(X.dWs)); CK(hipFree(X.dInfo)); CK(hipFree(X.dSteps));
+        }
+        if (!all_ok)
+            return 1; // (a wrong variant is not timed)
+        Problem X;
+        build(X, P, Q, false, 100);
+        const double flop = 8192.0 * X.products;
+        printf("front %d x %d destinations of 256 x 256, %d update(s) queued on each, full tiles: %zu workgroups, %.3f TFLOP per launch\n", P, P, Q, X.nwork, flop / 1e12);
+        for (int round = 0; round < 2; round++)
+            for (int which : kinds)
+            {
+                float best, mean;
+                time_kind(which, X, &best, &mean);
+                printf("time   Q = %d round %d  %-62s best %8.3f ms = %6.2f TFLOP/s, mean of 4 %8.3f ms = %6.2f\n", Q, round, name_of(which), best, flop / best / 1e9, mean, flop / mean / 1e9);
+            }
+        CK(hipFree(X.d)); CK(hipFree(X.dT)); CK(hipFree(X.dW)); CK(hipFree(X.dWs)); CK(hipFree(X.dInfo)); CK(hipFree(X.dSteps));
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     const int P = argc > 1 ? atoi(argv[1]) : 40, Q = argc > 2 ? atoi(argv[2]) : 1, fill = argc > 3 ? atoi(argv[3]) : 100;
+    if (argc > 4 && !strcmp(argv[4], "orders"))
+        return orders_mode(P);
     // ---- correctness on a small front: every entry of some destinations against a host product
     for (int cf : {100, 45})
     {
