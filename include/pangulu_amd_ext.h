@@ -170,7 +170,28 @@ extern "C"
 #define PANGULU_AMD_TRANS_H 2    /* A^H X = B (real value types: the same as _T) */
     int pangulu_amd_gstrs_trans(sparse_value_t *rhs, sparse_index_t nrhs, sparse_pointer_t ldb, int trans, pangulu_gstrs_options *gstrs_options,
                                 void **pangulu_handle);
-    /* what the last pangulu_amd_gstrs_multi / pangulu_amd_gstrs_trans on this handle did: columns swept on the device (0: host sweep), panel width used
+    /* The same solves for right-hand sides that already live on the device -- a preconditioner inside a Krylov loop on device
+     * vectors, a Newton step whose residual was just computed there.  `d_rhs` is a column-major ldb x nrhs matrix in DEVICE memory of
+     * the device the factors are on; column j is overwritten with the solution of op(A) x = column j, op by `trans` as above,
+     * permutation, padding rows and scaling as for pangulu_amd_gstrs_multi / _trans; rows n .. ldb - 1 of a column are not touched.
+     * Nothing is copied to the host: each panel of columns is brought into factor space, swept and brought back by kernels.  The
+     * work is ordered behind everything queued on `stream` (a hipStream_t; NULL: the legacy default stream) when the call is made
+     * and has completed on return, so the solutions are visible to every stream.  What does not depend on the right-hand sides stays
+     * on the device between calls and is rebuilt after pangulu_gstrf, pangulu_amd_update_values and pangulu_amd_reset_numeric;
+     * pangulu_finalize frees it.  Returns
+     *   0  success (nrhs = 0 included);
+     *   1  the handle has not been factorised;
+     *   2  d_rhs == NULL with nrhs > 0, ldb < n, or d_rhs is not device memory of that device holding ldb x nrhs values (asked of
+     *      the runtime on the host: a host pointer is refused, never handed to a kernel);
+     *   3  unknown `trans`;
+     *   4  no device-resident path for this handle -- several ranks, PANGULU_AMD_DEVICE_SOLVE=0, a host-memory platform, a platform
+     *      without the operator, or a transposed solve where the transposed kernels are not offered (PANGULU_HIP_SOLVE_CHUNKED=0):
+     *      stage through the host and call pangulu_amd_gstrs_multi / _trans.
+     * With 1 .. 4 nothing has been touched.  Every rank decides by its own arguments and state (no communication).
+     * pangulu_amd_last_solve_path and info.time_solve report the call like the host-pointer ones. */
+    int pangulu_amd_gstrs_device(sparse_value_t *d_rhs, sparse_index_t nrhs, sparse_pointer_t ldb, int trans, void *stream,
+                                 pangulu_gstrs_options *gstrs_options, void **pangulu_handle);
+    /* what the last pangulu_amd_gstrs_multi / pangulu_amd_gstrs_trans / pangulu_amd_gstrs_device on this handle did: columns swept on the device (0: host sweep), panel width used
      * (the widest panel; 1: column by column), number of panels.  Any pointer may be NULL.  Returns 0. */
     int pangulu_amd_last_solve_path(void **pangulu_handle, int *device_columns, int *panel_width, int *panels);
 

@@ -338,6 +338,36 @@ extern "C"
     int pangulu_platform_0201001_block_trsm_multi_trans(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *forward_ut,
                                                         const pangulu_hip_solve_sweep_t *backward_lt, int conjugate, calculate_type *X,
                                                         pangulu_uint64_t xlen, pangulu_uint64_t npanel, const int *w);
+    /* Optional: the same solves for right-hand sides that already live on the device.  `d_rhs` is a column-major ldb x nrhs matrix in
+     * DEVICE memory in the USER's ordering; column j is replaced by the solution of op(A) x = column j, mode 0 (A, `first` / `second`
+     * the lower / upper sweep as for block_trsm_multi), 1 (A^T) or 2 (A^H; the sweeps as for block_trsm_multi_trans).  The columns go
+     * through the panels w[0 .. npanel) in order (panel p takes the next min(w[p], columns left) columns); each panel is packed into
+     * factor space by a kernel, swept, and unpacked, through `maps`:
+     *     in:  X[i] = s_in[i] * rhs[in_idx[i]] (in_idx[i] == 0xffffffff: a padding row, 0);  out: rhs[out_idx[i]] = s_out[i] * X[i]
+     * for i < n (n <= xlen; indices < n_user <= ldb; s_in / s_out NULL: no scaling).  Rows n_user .. ldb - 1 of a column are not
+     * touched.  Everything that does not depend on the right-hand sides -- the descriptors of the sweeps, the panel buffer, the maps --
+     * stays on the device in `*workspace` (NULL before the first call), one part per direction built on first use.  It holds device
+     * addresses of the records the sweeps' slots point to: the caller releases it with solve_workspace_free before those records
+     * change, and when it is done.  The work is ordered behind everything queued on `caller_stream` (a hipStream_t; NULL: the
+     * legacy default stream) at the time of the call, runs on the back-end's stream without host synchronisation between the panels,
+     * and has completed on return.
+     * Returns the widest panel (npanel = 0 only asks and touches nothing); 0 where the kernels this mode needs are not offered (as
+     * block_trsm_multi_trans; nothing is touched); -1 if d_rhs is not device memory of the back-end's device holding ldb x nrhs values
+     * (decided on the host from the pointer's attributes, before any launch). */
+    typedef struct pangulu_hip_solve_maps_t
+    {
+        pangulu_uint64_t n, n_user;
+        const unsigned int *in_idx, *out_idx;
+        const double *s_in, *s_out;
+    } pangulu_hip_solve_maps_t;
+    int pangulu_platform_0201001_block_trsm_multi_device(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *first,
+                                                         const pangulu_hip_solve_sweep_t *second, int mode, calculate_type *d_rhs,
+                                                         pangulu_uint64_t ldb, pangulu_uint64_t nrhs, pangulu_uint64_t npanel, const int *w,
+                                                         pangulu_uint64_t xlen, const pangulu_hip_solve_maps_t *maps, void **workspace,
+                                                         void *caller_stream);
+    void pangulu_platform_0201001_solve_workspace_free(void **workspace);
+    /* Device bytes held by all solve workspaces that are alive. */
+    unsigned long long pangulu_platform_0201001_get_solve_workspace_bytes(void);
     /* Optional: y[dst segment] += A_blk * x[src segment] for a list of device-resident block records, in one launch (one
      * workgroup per block, floating-point atomics on y).  `x` and `y` are HOST vectors of `xlen` values (nb per block
      * row / column); y is read, updated and written back.  csr[i] != 0: the record is an upper diagonal half (CSR, diagonal

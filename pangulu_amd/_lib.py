@@ -168,6 +168,8 @@ def load(vtype="r64", test_hooks=False):
     lib.pangulu_amd_gstrs_multi.restype = ctypes.c_int
     lib.pangulu_amd_gstrs_trans.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(GstrsOptions), vpp]
     lib.pangulu_amd_gstrs_trans.restype = ctypes.c_int
+    lib.pangulu_amd_gstrs_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, vp, ctypes.POINTER(GstrsOptions), vpp]
+    lib.pangulu_amd_gstrs_device.restype = ctypes.c_int
     lib.pangulu_amd_last_solve_path.argtypes = [vpp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.pangulu_amd_last_solve_path.restype = ctypes.c_int
     lib.pangulu_gssv.argtypes = [vp, ctypes.POINTER(GstrfOptions), ctypes.POINTER(GstrsOptions), vpp]
@@ -240,6 +242,7 @@ def load(vtype="r64", test_hooks=False):
     lib.pangulu_platform_0201001_get_stats.argtypes = [ctypes.POINTER(HipStats), ctypes.c_int]
     lib.pangulu_platform_0201001_get_stats.restype = None
     lib.pangulu_platform_0201001_get_stream.restype = ctypes.c_void_p
+    lib.pangulu_platform_0201001_get_solve_workspace_bytes.restype = ctypes.c_ulonglong
     _cache[key] = lib
     return lib
 

@@ -81,6 +81,8 @@ void bind_builtin_hip(Platform &p)
     p.block_trsv = pangulu_platform_0201001_block_trsv;
     p.block_trsm_multi = pangulu_platform_0201001_block_trsm_multi;
     p.block_trsm_multi_trans = pangulu_platform_0201001_block_trsm_multi_trans;
+    p.block_trsm_multi_device = pangulu_platform_0201001_block_trsm_multi_device;
+    p.solve_workspace_free = pangulu_platform_0201001_solve_workspace_free;
     p.block_spmv_add = pangulu_platform_0201001_block_spmv_add;
     p.schedule = pangulu_platform_0201001_schedule;
     p.schedule_range = pangulu_platform_0201001_schedule_range;
@@ -145,61 +147,75 @@ inline val_t value_times(val_t v, double s)
     return (val_t)(v * s);
 #endif
 }
-void rhs_to_factor_space(const Solver &S, const val_t *rhs, val_t *b)
+} // namespace
+
+// The one place that knows how: the maps of SolveMaps (pg_host.h) for a direction, built on first use.  Row i of the factors' ordering
+// is row / column j = perm[i] of the scaled matrix A1 = Dr A Q Dc (q = match_col), a padding row where j >= n_user.
+//   A x = b:       A1 y = Dr b, x[q(j)] = dc[q(j)] y[j]:   in (j, dr[j]), out (q(j), dc[q(j)])
+//   A^T x = b:     (A1^T z)[j] = sum_i A1[i, j] z[i] = dc[q(j)] sum_i A[i, q(j)] (dr[i] z[i]) = dc[q(j)] (A^T x)[q(j)] with x[i] = dr[i] z[i],
+//                  so A1^T z = c with c[j] = dc[q(j)] b[q(j)] gives x = Dr z: the roles of the scalings swap, and the matching moves to
+//                  the way in (b lives in the column space of A, z in its row space):   in (q(j), dc[q(j)]), out (j, dr[j])
+// Dr and Dc are real, so A^H x = b takes the transposed pair.  The symmetric permutation is the same both ways: Ap^T = P A1^T P^T.
+// Without scaling q is the identity and the scale arrays stay empty.
+const SolveMaps &pg::solve_maps(Solver &S, bool transposed)
 {
+    SolveMaps &M = S.solve_maps[transposed ? 1 : 0];
+    if (M.ready)
+        return M;
     const bool scaled = !S.scale_row.empty();
-    for (u32 i = 0; i < S.n; i++)
+    std::vector<u32> row_idx(S.n, SOLVE_MAP_PAD), col_idx(S.n, SOLVE_MAP_PAD);
+    std::vector<double> row_s, col_s;
+    if (scaled)
     {
-        if (S.perm[i] < S.n_user)
-            b[i] = scaled ? value_times(rhs[S.perm[i]], S.scale_row[S.perm[i]]) : rhs[S.perm[i]]; // A1 y = Dr b
-        else
-            memset(&b[i], 0, sizeof(val_t)); // padding row: 1 * x = 0
+        row_s.assign(S.n, 0.0);
+        col_s.assign(S.n, 0.0);
     }
-}
-void solution_from_factor_space(const Solver &S, const val_t *b, val_t *rhs)
-{
-    if (S.scale_row.empty())
-    {
-        for (u32 i = 0; i < S.n; i++)
-            if (S.perm[i] < S.n_user)
-                rhs[S.perm[i]] = b[i];
-        return;
-    }
-    // y (in the scaled matrix's column order) -> x[q(i)] = dc[q(i)] y[i]
-    std::vector<val_t> y(S.n_user);
-    for (u32 i = 0; i < S.n; i++)
-        if (S.perm[i] < S.n_user)
-            y[S.perm[i]] = b[i];
-    for (u32 i = 0; i < S.n_user; i++)
-        rhs[S.match_col[i]] = value_times(y[i], S.scale_col[S.match_col[i]]);
-}
-// The transposed pair (pangulu_amd_gstrs_trans).  The factors are those of Ap = P A1 P^T with perm[new] = old, and on a handle with
-// scaling on A1 = Dr A Q Dc, that is A1[i, j] = dr[i] A[i, q(j)] dc[q(j)] with q = match_col.  For A^T x = b:
-//     (A1^T z)[j] = sum_i A1[i, j] z[i] = dc[q(j)] sum_i A[i, q(j)] (dr[i] z[i]) = dc[q(j)] (A^T x)[q(j)]   with x[i] = dr[i] z[i],
-// so A1^T z = c with c[j] = dc[q(j)] b[q(j)] gives x = Dr z: the roles of the scalings swap, and the matching moves to the way in
-// (b lives in the column space of A, z in its row space).  Dr and Dc are real, so A^H x = b takes the same pair.  The symmetric
-// permutation is the same as above: Ap^T = P A1^T P^T; a padding row stays 1 * z = 0.
-void rhs_to_factor_space_trans(const Solver &S, const val_t *rhs, val_t *b)
-{
-    const bool scaled = !S.scale_row.empty();
     for (u32 i = 0; i < S.n; i++)
     {
-        const u32 j = S.perm[i]; // column of A1
+        const u32 j = S.perm[i];
         if (j >= S.n_user)
+            continue;
+        row_idx[i] = j;
+        col_idx[i] = scaled ? S.match_col[j] : j;
+        if (scaled)
+        {
+            row_s[i] = S.scale_row[j];
+            col_s[i] = S.scale_col[S.match_col[j]];
+        }
+    }
+    M.in_idx = transposed ? col_idx : row_idx;
+    M.out_idx = transposed ? row_idx : col_idx;
+    M.s_in = transposed ? col_s : row_s;
+    M.s_out = transposed ? row_s : col_s;
+    M.ready = true;
+    return M;
+}
+
+namespace
+{
+// b = the right-hand side in factor space; a padding row: 1 * x = 0
+void rhs_into_factor_space(const SolveMaps &M, u32 n, const val_t *rhs, val_t *b)
+{
+    const bool scaled = !M.s_in.empty();
+    for (u32 i = 0; i < n; i++)
+    {
+        if (M.in_idx[i] == SOLVE_MAP_PAD)
             memset(&b[i], 0, sizeof(val_t));
-        else if (scaled)
-            b[i] = value_times(rhs[S.match_col[j]], S.scale_col[S.match_col[j]]); // c[j] = dc[q(j)] b[q(j)]
         else
-            b[i] = rhs[j];
+            b[i] = scaled ? value_times(rhs[M.in_idx[i]], M.s_in[i]) : rhs[M.in_idx[i]];
     }
 }
-void solution_from_factor_space_trans(const Solver &S, const val_t *b, val_t *rhs)
+void solution_out_of_factor_space(const SolveMaps &M, u32 n, const val_t *b, val_t *rhs)
 {
-    const bool scaled = !S.scale_row.empty();
-    for (u32 i = 0; i < S.n; i++)
-        if (S.perm[i] < S.n_user)
-            rhs[S.perm[i]] = scaled ? value_times(b[i], S.scale_row[S.perm[i]]) : b[i]; // x = Dr z
+    const bool scaled = !M.s_out.empty();
+    for (u32 i = 0; i < n; i++)
+        if (M.out_idx[i] != SOLVE_MAP_PAD)
+            rhs[M.out_idx[i]] = scaled ? value_times(b[i], M.s_out[i]) : b[i];
 }
+void rhs_to_factor_space(Solver &S, const val_t *rhs, val_t *b) { rhs_into_factor_space(solve_maps(S, false), S.n, rhs, b); }
+void solution_from_factor_space(Solver &S, const val_t *b, val_t *rhs) { solution_out_of_factor_space(solve_maps(S, false), S.n, b, rhs); }
+void rhs_to_factor_space_trans(Solver &S, const val_t *rhs, val_t *b) { rhs_into_factor_space(solve_maps(S, true), S.n, rhs, b); }
+void solution_from_factor_space_trans(Solver &S, const val_t *b, val_t *rhs) { solution_out_of_factor_space(solve_maps(S, true), S.n, b, rhs); }
 } // namespace
 
 extern "C"
@@ -260,6 +276,11 @@ extern "C"
         snprintf(sym, sizeof(sym), "pangulu_platform_%07x_block_trsm_multi_trans", platform_id);
         p.block_trsm_multi_trans = (int (*)(pangulu_inblock_idx, const pangulu_hip_solve_sweep_t *, const pangulu_hip_solve_sweep_t *, int, val_t *,
                                             pangulu_uint64_t, pangulu_uint64_t, const int *))dlsym(h, sym);
+        // ... and the solve of device-resident right-hand sides to pangulu_amd_gstrs_device's return code 4
+        snprintf(sym, sizeof(sym), "pangulu_platform_%07x_block_trsm_multi_device", platform_id);
+        p.block_trsm_multi_device = (decltype(p.block_trsm_multi_device))dlsym(h, sym);
+        snprintf(sym, sizeof(sym), "pangulu_platform_%07x_solve_workspace_free", platform_id);
+        p.solve_workspace_free = (decltype(p.solve_workspace_free))dlsym(h, sym);
         int (*sz)() = (int (*)())dlsym(h, "pangulu_oracle_sizeof_value");
         if (sz && sz() != (int)sizeof(val_t))
         {
@@ -722,6 +743,7 @@ extern "C"
         if (S->analysis_only)
             fatal("PANGULU_AMD_ANALYSIS_ONLY handle: pattern, mapping and models only, nothing to factorise");
         NearDevice near(active_platform());
+        drop_solve_workspace(*S); // (its descriptors hold device addresses of the records this call rewrites)
         numeric_factorize(*S);
     }
 
@@ -836,6 +858,32 @@ extern "C"
                 solution_from_factor_space_trans(*S, b.data() + (size_t)j * S->n, rhs + (size_t)j * ldb);
         S->info.time_solve = wall_seconds() - t0;
         return 0;
+    }
+
+    int pangulu_amd_gstrs_device(sparse_value_t *d_rhs, sparse_index_t nrhs, sparse_pointer_t ldb, int trans, void *stream,
+                                 pangulu_gstrs_options *gstrs_options, void **pangulu_handle)
+    {
+        if (gstrs_options == nullptr)
+        {
+            if (world()->rank == 0)
+                printf("[PanguLU ERROR] Invalid input parameter. gstrs option struct pointer is NULL. Exit.\n");
+            exit(1);
+        }
+        Solver *S = (Solver *)*pangulu_handle;
+        if (!S->factored)
+            return 1;
+        const double t0 = wall_seconds();
+        if (trans != PANGULU_AMD_TRANS_NONE && trans != PANGULU_AMD_TRANS_T && trans != PANGULU_AMD_TRANS_H)
+            return 3;
+        if (nrhs != 0 && (d_rhs == nullptr || ldb < (sparse_pointer_t)S->n_user))
+            return 2;
+        if (nrhs == 0)
+            return 0;
+        NearDevice near(active_platform());
+        const int rc = triangular_solve_device(*S, d_rhs, (u32)nrhs, (u64)ldb, trans, stream);
+        if (rc == 0)
+            S->info.time_solve = wall_seconds() - t0;
+        return rc;
     }
 
     int pangulu_amd_last_solve_path(void **pangulu_handle, int *device_columns, int *panel_width, int *panels)
@@ -1003,6 +1051,7 @@ extern "C"
             }
         }
         NearDevice near(active_platform());
+        drop_solve_workspace(*S);
         reload_values(*S, B);
         if (S->arena_snapshot)
             pangulu_amd_snapshot(pangulu_handle); // (bench-style resets restore the NEW values)
@@ -1112,6 +1161,7 @@ extern "C"
         Platform &plat = active_platform();
         if (!S->arena_snapshot)
             return 1;
+        drop_solve_workspace(*S);
         plat.synchronize();
         if (plat.host_memory)
             plat.memcpy_(S->storage.darena, S->arena_snapshot, S->storage.arena_bytes, 2);

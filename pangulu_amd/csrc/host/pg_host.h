@@ -86,6 +86,12 @@ struct Platform
     // optional: the transposed solve on the device (0 returned: not offered at this nb / with these switches)
     int (*block_trsm_multi_trans)(pangulu_inblock_idx, const pangulu_hip_solve_sweep_t *, const pangulu_hip_solve_sweep_t *, int, val_t *,
                                   pangulu_uint64_t, pangulu_uint64_t, const int *) = nullptr;
+    // optional: the solve of right-hand sides that live on the device, on a workspace the back-end keeps per handle (0 returned:
+    // not offered; < 0: the pointer was refused), and the release of that workspace
+    int (*block_trsm_multi_device)(pangulu_inblock_idx, const pangulu_hip_solve_sweep_t *, const pangulu_hip_solve_sweep_t *, int, val_t *,
+                                   pangulu_uint64_t, pangulu_uint64_t, pangulu_uint64_t, const int *, pangulu_uint64_t,
+                                   const pangulu_hip_solve_maps_t *, void **, void *) = nullptr;
+    void (*solve_workspace_free)(void **) = nullptr;
 };
 Platform &active_platform();               // built-in HIP unless the test hook replaced it
 bool platform_is_builtin_hip();
@@ -321,6 +327,20 @@ struct SolveSweepPlan
     std::vector<pangulu_exblock_idx> blk_bcol;
 };
 
+// How one right-hand side gets into factor space and its solution out of it (pangulu_gstrs and all its relatives), as a gather and a
+// scatter over the rows i of the factors' ordering with an optional real scale per row:
+//     b[i] = s_in[i] * rhs[in_idx[i]]   (a padding row, in_idx[i] == SOLVE_MAP_PAD, gives 0);   x[out_idx[i]] = s_out[i] * z[i]   (skipped there)
+// -- the symmetric permutation with its padding rows and, on a handle with scaling on, the matching and both scalings (s_in / s_out
+// empty otherwise).  One pair per direction, [0] A x = b and [1] A^T x = b / A^H x = b (pg_api.cpp: solve_maps()); the host loops
+// and the pack / unpack kernels of the device-resident solve read the same arrays.
+constexpr u32 SOLVE_MAP_PAD = 0xffffffffu;
+struct SolveMaps
+{
+    std::vector<u32> in_idx, out_idx;
+    std::vector<double> s_in, s_out;
+    bool ready = false;
+};
+
 struct Solver
 {
     // configuration
@@ -366,6 +386,10 @@ struct Solver
     SolveSweepPlan solve_plan_trans[2];
     bool solve_plan_trans_ready = false;
     int last_solve_device_columns = 0, last_solve_panel_width = 0, last_solve_panels = 0;
+    SolveMaps solve_maps[2];               // [0] untransposed, [1] transposed: built on first use, fixed for the handle's life
+    // pangulu_amd_gstrs_device: what the back-end keeps on the device for this handle between calls (descriptors of the sweeps, panel
+    // buffer, the maps).  It holds device addresses of records: dropped whenever the factors are about to change (drop_solve_workspace)
+    void *solve_workspace = nullptr;
     // Multi-rank replay (round 4, PANGULU_AMD_MULTI_REPLAY=1): what THIS rank did in its first factorisation, in order -- the ranges
     // of the back-end's recorded operations its platform calls produced, the markers between them with the blocks that were
     // announced behind each, and which blocks of other ranks had arrived (into which receive slot) before each call was made.
@@ -452,6 +476,11 @@ void triangular_solve_multi(Solver &S, val_t *B, u32 nrhs); // the same for n x 
 // A^T X = B (conjugate = false) or A^H X = B on the same factors, same layout and collectiveness as triangular_solve_multi: panels
 // through Platform::block_trsm_multi_trans where the device solve runs and offers it, the host sweep over block columns elsewhere
 void triangular_solve_multi_trans(Solver &S, val_t *B, u32 nrhs, bool conjugate);
+const SolveMaps &solve_maps(Solver &S, bool transposed);  // pg_api.cpp: the handle's maps for a direction, built on first use (rank 0)
+// The same solves for an ldb x nrhs column-major matrix in DEVICE memory, in and out of factor space on the device through solve_maps(),
+// ordered behind `stream` (one rank).  0: done; 2: the back-end refused the pointer; 4: no device-resident path for this handle (nothing touched)
+int triangular_solve_device(Solver &S, val_t *d_rhs, u32 nrhs, u64 ldb, int trans, void *stream);
+void drop_solve_workspace(Solver &S);                     // before the factors change, and when the handle goes
 double factor_check(Solver &S);                           // ||L(U 1) - A 1|| / ||A 1|| on the factors where they are (pg_check.cpp; collective)
 double factor_check_vectors(Solver &S, int nvec, unsigned long long seed); // the same on the ones vector + nvec - 1 random +-1 vectors: the worst quotient
 void compute_task_model(Solver &S, double hbm_bytes_per_s, double fp_flops_per_s); // pg_model.cpp: T* of SURVEY.md §8d

@@ -1047,6 +1047,7 @@ void download_factors(Solver &S)
 Solver::~Solver()
 {
     Platform &plat = active_platform();
+    drop_solve_workspace(*this);
     if (schedule_recorded && plat.schedule)
         plat.schedule(0, this); // the recorded launches point into this handle's arena and mirrors
     for (char *c : snapshot_dchunks)

@@ -226,12 +226,8 @@ static bool device_solve_enabled(const Solver &S, const Platform &plat)
     return !(S.nproc != 1 || plat.host_memory || !plat.block_trsv || (e && atoi(e) == 0));
 }
 
-// Single rank on a device: both sweeps on the device-resident factors (no download of the factors), level by level of the block
-// dependency graph.  X holds `npanel` panels one after the other, panel p with nbk*nb x w[p] values, right-hand side fastest: one
-// pangulu_platform_0201001_block_trsm_multi call; a platform with block_trsv alone takes single columns (w[p] = 1), sweep by sweep.
-// The plans of both sweeps are built on first use and kept on the handle.  trans = PANGULU_AMD_TRANS_T / _H: the transposed sweeps
-// (U^T forward, L^T backward) on plans of their own through Platform::block_trsm_multi_trans, which the caller has found to be offered.
-static void device_solve_panels(Solver &S, Platform &plat, val_t *X, size_t npanel, const int *w, int trans = PANGULU_AMD_TRANS_NONE)
+// the two sweeps of a direction as the platform operators take them, from the handle's plans (built here on first use)
+static void solve_sweeps_of(Solver &S, int trans, pangulu_hip_solve_sweep_t sw[2])
 {
     if (trans == PANGULU_AMD_TRANS_NONE && !S.solve_plan_ready)
     {
@@ -245,7 +241,6 @@ static void device_solve_panels(Solver &S, Platform &plat, val_t *X, size_t npan
         build_trans_sweep_plan(S, false, S.solve_plan_trans[1]);
         S.solve_plan_trans_ready = true;
     }
-    pangulu_hip_solve_sweep_t sw[2];
     for (int s = 0; s < 2; s++)
     {
         const SolveSweepPlan &pl = trans == PANGULU_AMD_TRANS_NONE ? S.solve_plan[s] : S.solve_plan_trans[s];
@@ -255,6 +250,17 @@ static void device_solve_panels(Solver &S, Platform &plat, val_t *X, size_t npan
         sw[s].blk_slots = pl.blk_slots.data();
         sw[s].blk_bcol = pl.blk_bcol.data();
     }
+}
+
+// Single rank on a device: both sweeps on the device-resident factors (no download of the factors), level by level of the block
+// dependency graph.  X holds `npanel` panels one after the other, panel p with nbk*nb x w[p] values, right-hand side fastest: one
+// pangulu_platform_0201001_block_trsm_multi call; a platform with block_trsv alone takes single columns (w[p] = 1), sweep by sweep.
+// The plans of both sweeps are built on first use and kept on the handle.  trans = PANGULU_AMD_TRANS_T / _H: the transposed sweeps
+// (U^T forward, L^T backward) on plans of their own through Platform::block_trsm_multi_trans, which the caller has found to be offered.
+static void device_solve_panels(Solver &S, Platform &plat, val_t *X, size_t npanel, const int *w, int trans = PANGULU_AMD_TRANS_NONE)
+{
+    pangulu_hip_solve_sweep_t sw[2];
+    solve_sweeps_of(S, trans, sw);
     const pangulu_uint64_t xlen = (pangulu_uint64_t)S.nbk * S.nb;
     if (trans != PANGULU_AMD_TRANS_NONE)
     {
@@ -350,23 +356,30 @@ void triangular_solve(Solver &S, val_t *rhs)
     std::copy(x.begin(), x.begin() + S.n, rhs);
 }
 
-// the columns of Bm in panels through the device sweeps (trans: which pair), panels at most wmax wide
-static void device_solve_columns(Solver &S, Platform &plat, val_t *Bm, u32 nrhs, int wmax, int trans)
+// panels for nrhs columns: the widest width while that many columns are left, then the smallest power of two that holds the rest (zero columns pad it)
+static std::vector<int> solve_panel_widths(u32 nrhs, int wmax)
 {
-    S.last_solve_device_columns = (int)nrhs;
-    const u32 nb = S.nb, n = S.n;
-    // panels: the widest width while that many columns are left, then the smallest power of two that holds the rest (zero columns pad it)
     std::vector<int> w;
-    size_t total_w = 0;
     for (u32 left = nrhs; left;)
     {
         int wp = 1;
         while (wp < wmax && (u32)wp < left)
             wp <<= 1;
         w.push_back(wp);
-        total_w += (size_t)wp;
         left -= std::min(left, (u32)wp);
     }
+    return w;
+}
+
+// the columns of Bm in panels through the device sweeps (trans: which pair), panels at most wmax wide
+static void device_solve_columns(Solver &S, Platform &plat, val_t *Bm, u32 nrhs, int wmax, int trans)
+{
+    S.last_solve_device_columns = (int)nrhs;
+    const u32 nb = S.nb, n = S.n;
+    const std::vector<int> w = solve_panel_widths(nrhs, wmax);
+    size_t total_w = 0;
+    for (int wp : w)
+        total_w += (size_t)wp;
     const size_t xlen = (size_t)S.nbk * nb;
     std::vector<val_t> X(xlen * total_w, vmake(0));
     auto each_panel = [&](auto &&f)
@@ -504,6 +517,49 @@ void triangular_solve_multi_trans(Solver &S, val_t *Bm, u32 nrhs, bool conjugate
         return;
     }
     device_solve_columns(S, plat, Bm, nrhs, wmax, conjugate ? PANGULU_AMD_TRANS_H : PANGULU_AMD_TRANS_T);
+}
+
+// pangulu_amd_gstrs_device: the columns of a device matrix through Platform::block_trsm_multi_device, which packs, sweeps and unpacks
+// each panel on the device and keeps what does not depend on the right-hand sides in S.solve_workspace.  Every condition for 4 is
+// this rank's own (no exchange), and nothing has been touched when it is returned.
+int triangular_solve_device(Solver &S, val_t *d_rhs, u32 nrhs, u64 ldb, int trans, void *stream)
+{
+    Platform &plat = active_platform();
+    if (!device_solve_enabled(S, plat) || !plat.block_trsm_multi_device || !plat.solve_workspace_free)
+        return 4;
+    const pangulu_uint64_t xlen = (pangulu_uint64_t)S.nbk * S.nb;
+    const int wmax = plat.block_trsm_multi_device((pangulu_inblock_idx)S.nb, nullptr, nullptr, trans, nullptr, 0, 0, 0, nullptr, xlen, nullptr, nullptr, nullptr);
+    if (wmax < 1)
+        return 4;
+    const SolveMaps &M = solve_maps(S, trans != PANGULU_AMD_TRANS_NONE);
+    pangulu_hip_solve_maps_t maps;
+    maps.n = S.n;
+    maps.n_user = S.n_user;
+    maps.in_idx = M.in_idx.data();
+    maps.out_idx = M.out_idx.data();
+    maps.s_in = M.s_in.empty() ? nullptr : M.s_in.data();
+    maps.s_out = M.s_out.empty() ? nullptr : M.s_out.data();
+    pangulu_hip_solve_sweep_t sw[2];
+    solve_sweeps_of(S, trans, sw);
+    const std::vector<int> w = solve_panel_widths(nrhs, wmax);
+    const int rc = plat.block_trsm_multi_device((pangulu_inblock_idx)S.nb, &sw[0], &sw[1], trans, d_rhs, ldb, nrhs, (pangulu_uint64_t)w.size(), w.data(), xlen,
+                                                &maps, &S.solve_workspace, stream);
+    if (rc < 0)
+        return 2;
+    if (rc == 0)
+        return 4;
+    S.last_solve_device_columns = (int)nrhs;
+    S.last_solve_panel_width = w[0];
+    S.last_solve_panels = (int)w.size();
+    return 0;
+}
+
+void drop_solve_workspace(Solver &S)
+{
+    if (!S.solve_workspace)
+        return;
+    active_platform().solve_workspace_free(&S.solve_workspace);
+    S.solve_workspace = nullptr;
 }
 
 } // namespace pg

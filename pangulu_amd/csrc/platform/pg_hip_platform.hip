@@ -871,11 +871,12 @@ int solve_widest_panel(size_t nb)
     return wmax;
 }
 
-// what one sweep of a solve call has on the device: its rows and blocks start at row0 / blk0 of the call's descriptor arrays
+// what one sweep of a solve has on the device: its rows and blocks start at row0 / blk0 of the descriptor arrays it shares with the
+// other sweep; the rows of level l are level_ptr[l] .. level_ptr[l + 1] (a copy: a workspace outlives the host's description)
 struct SolveSweepD
 {
     int mode; // SOLVE_LOWER / SOLVE_UPPER, or a transposed mode
-    const pangulu_hip_solve_sweep_t *sw;
+    std::vector<pangulu_uint64_t> level_ptr;
     size_t row0, blk0;
     std::vector<size_t> blk_level_ptr;
 };
@@ -952,21 +953,75 @@ void launch_solve_level(int mode, bool by_column, int nb, int ch, size_t nbl, si
 
 // the launches of one panel of W right-hand sides in d_x: the sweeps one after the other, a gather and a level launch per level
 template <int W>
-void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, const SolveRowD *d_rows, const SolveBlkD *d_blks, val_t *d_x)
+void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, int conj, const SolveRowD *d_rows, const SolveBlkD *d_blks, val_t *d_x)
 {
     const bool by_column = W == 1 && solve_by_column((size_t)nb);
     const int ch = by_column ? 0 : solve_multi_chunk((size_t)nb, W, SOLVE_LDS_BUDGET);
     for (const SolveSweepD &S : sweeps)
-        for (size_t l = 0; l < (size_t)S.sw->nlevel; l++)
+        for (size_t l = 0; l + 1 < S.level_ptr.size(); l++)
         {
-            const pangulu_uint64_t *lp = S.sw->level_ptr;
+            const pangulu_uint64_t *lp = S.level_ptr.data();
             const size_t n = (size_t)(lp[l + 1] - lp[l]), nbl = S.blk_level_ptr[l + 1] - S.blk_level_ptr[l];
             if (!n)
                 continue;
             const SolveBlkD *blks = d_blks + S.blk0 + S.blk_level_ptr[l];
             const SolveRowD *rows = d_rows + S.row0 + lp[l];
-            launch_solve_level<W>(S.mode, by_column, nb, ch, nbl, n, blks, rows, d_x);
+            launch_solve_level<W>(S.mode | conj, by_column, nb, ch, nbl, n, blks, rows, d_x);
         }
+}
+
+// ... of a panel of w right-hand sides, w a width solve_widest_panel() allows.  conj: SOLVE_CONJ on top of the sweeps' (transposed) modes, or 0
+void launch_solve_panel_of(int w, int nb, const std::vector<SolveSweepD> &sweeps, int conj, const SolveRowD *d_rows, const SolveBlkD *d_blks, val_t *d_x)
+{
+    switch (w)
+    {
+    case 1:
+        launch_solve_panel<1>(nb, sweeps, conj, d_rows, d_blks, d_x);
+        break;
+    case 2:
+        launch_solve_panel<2>(nb, sweeps, conj, d_rows, d_blks, d_x);
+        break;
+    case 4:
+        launch_solve_panel<4>(nb, sweeps, conj, d_rows, d_blks, d_x);
+        break;
+    case 8:
+        launch_solve_panel<8>(nb, sweeps, conj, d_rows, d_blks, d_x);
+        break;
+    default:
+        launch_solve_panel<16>(nb, sweeps, conj, d_rows, d_blks, d_x);
+        break;
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+// What every solve on the device-resident factors does first, B.mutex held: whatever still writes factor records -- a held
+// factorisation, the records stream, background updates -- is ordered before what B.stream gets next
+void solve_join_factor_streams()
+{
+    flush_pending_getrf();
+    HIP_CHECK(hipSetDevice(B.device));
+    join_records(B.stream); // the sparse records of finished blocks are written on the records stream
+    join_background(B.stream);
+}
+
+// The descriptors of the given sweeps (one, or the lower and then the upper one; or U^T and then L^T), one after the other in hr / hb
+// (never empty afterwards: they are allocated as they are)
+void build_solve_sweeps(const std::vector<const pangulu_hip_solve_sweep_t *> &sw, const std::vector<int> &mode, std::vector<SolveRowD> &hr,
+                        std::vector<SolveBlkD> &hb, std::vector<SolveSweepD> &sweeps)
+{
+    sweeps.assign(sw.size(), SolveSweepD());
+    for (size_t s = 0; s < sw.size(); s++)
+    {
+        sweeps[s].mode = mode[s];
+        sweeps[s].level_ptr.assign(sw[s]->level_ptr, sw[s]->level_ptr + sw[s]->nlevel + 1);
+        sweeps[s].row0 = hr.size();
+        sweeps[s].blk0 = hb.size();
+        append_solve_descriptors(mode[s], *sw[s], hr, hb, sweeps[s].blk_level_ptr);
+    }
+    if (hr.empty())
+        hr.resize(1);
+    if (hb.empty())
+        hb.resize(1);
 }
 
 // The level-scheduled block triangular solve, both operators' body: the descriptors of the given sweeps (one, or the lower and then
@@ -977,25 +1032,11 @@ void block_solve_panels(int nb, const std::vector<const pangulu_hip_solve_sweep_
 {
     ensure_ready();
     std::lock_guard<std::mutex> g(B.mutex);
-    flush_pending_getrf();
-    HIP_CHECK(hipSetDevice(B.device));
-    join_records(B.stream); // the sparse records of finished blocks are written on the records stream
-    join_background(B.stream);
+    solve_join_factor_streams();
     std::vector<SolveRowD> hr;
     std::vector<SolveBlkD> hb;
-    std::vector<SolveSweepD> sweeps(sw.size());
-    for (size_t s = 0; s < sw.size(); s++)
-    {
-        sweeps[s].mode = mode[s];
-        sweeps[s].sw = sw[s];
-        sweeps[s].row0 = hr.size();
-        sweeps[s].blk0 = hb.size();
-        append_solve_descriptors(mode[s], *sw[s], hr, hb, sweeps[s].blk_level_ptr);
-    }
-    if (hr.empty())
-        hr.resize(1);
-    if (hb.empty())
-        hb.resize(1);
+    std::vector<SolveSweepD> sweeps;
+    build_solve_sweeps(sw, mode, hr, hb, sweeps);
     const int wtop = *std::max_element(w, w + npanel);
     SolveRowD *d_rows = nullptr;
     SolveBlkD *d_blks = nullptr;
@@ -1009,25 +1050,7 @@ void block_solve_panels(int nb, const std::vector<const pangulu_hip_solve_sweep_
     {
         const size_t bytes = sizeof(val_t) * xlen * (size_t)w[p];
         HIP_CHECK(hipMemcpyAsync(d_x, X, bytes, hipMemcpyHostToDevice, B.stream));
-        switch (w[p])
-        {
-        case 1:
-            launch_solve_panel<1>(nb, sweeps, d_rows, d_blks, d_x);
-            break;
-        case 2:
-            launch_solve_panel<2>(nb, sweeps, d_rows, d_blks, d_x);
-            break;
-        case 4:
-            launch_solve_panel<4>(nb, sweeps, d_rows, d_blks, d_x);
-            break;
-        case 8:
-            launch_solve_panel<8>(nb, sweeps, d_rows, d_blks, d_x);
-            break;
-        default:
-            launch_solve_panel<16>(nb, sweeps, d_rows, d_blks, d_x);
-            break;
-        }
-        HIP_CHECK(hipGetLastError());
+        launch_solve_panel_of(w[p], nb, sweeps, 0, d_rows, d_blks, d_x);
         HIP_CHECK(hipMemcpyAsync(X, d_x, bytes, hipMemcpyDeviceToHost, B.stream));
         X += xlen * (size_t)w[p];
     }
@@ -1035,6 +1058,112 @@ void block_solve_panels(int nb, const std::vector<const pangulu_hip_solve_sweep_
     HIP_CHECK(hipFree(d_rows));
     HIP_CHECK(hipFree(d_blks));
     HIP_CHECK(hipFree(d_x));
+}
+
+#include "pg_hip_solve_pack.h"
+
+// What a handle's device-resident solves keep on the device between calls (pangulu_platform_0201001_block_trsm_multi_device): per
+// direction ([0] A, [1] A^T and A^H) the descriptors of both sweeps and the index/scale maps, each built on first use, and one panel
+// buffer.  The descriptors hold device addresses of block records: the host frees the workspace before the records change.
+struct SolveWorkspace
+{
+    struct Direction
+    {
+        bool ready = false;
+        std::vector<SolveSweepD> sweeps;
+        SolveRowD *d_rows = nullptr;
+        SolveBlkD *d_blks = nullptr;
+        u32 *d_in_idx = nullptr, *d_out_idx = nullptr;
+        double *d_s_in = nullptr, *d_s_out = nullptr;
+    } dir[2];
+    int nb = 0;
+    size_t xlen = 0, n = 0;
+    val_t *d_x = nullptr; // xlen x the widest panel
+    hipEvent_t after_caller = nullptr;
+    size_t bytes = 0;
+};
+size_t g_solve_workspace_bytes = 0; // (under B.mutex)
+
+template <class T>
+void solve_workspace_alloc(SolveWorkspace &ws, T **p, size_t count)
+{
+    HIP_CHECK(hipMalloc((void **)p, sizeof(T) * count));
+    ws.bytes += sizeof(T) * count;
+    g_solve_workspace_bytes += sizeof(T) * count;
+}
+
+void solve_workspace_release(SolveWorkspace *ws) // B.mutex held
+{
+    HIP_CHECK(hipSetDevice(B.device));
+    HIP_CHECK(hipStreamSynchronize(B.stream));
+    for (SolveWorkspace::Direction &D : ws->dir)
+        for (void *p : {(void *)D.d_rows, (void *)D.d_blks, (void *)D.d_in_idx, (void *)D.d_out_idx, (void *)D.d_s_in, (void *)D.d_s_out})
+            if (p)
+                HIP_CHECK(hipFree(p));
+    if (ws->d_x)
+        HIP_CHECK(hipFree(ws->d_x));
+    if (ws->after_caller)
+        HIP_CHECK(hipEventDestroy(ws->after_caller));
+    g_solve_workspace_bytes -= ws->bytes;
+    delete ws;
+}
+
+// true: [p, p + bytes) is device memory of the back-end's device.  Asked of the runtime on the host: no kernel sees a pointer that fails.
+bool solve_pointer_on_device(const void *p, size_t bytes)
+{
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof(attr));
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess)
+    {
+        (void)hipGetLastError(); // (an unregistered host pointer is reported as an error: not one of ours)
+        return false;
+    }
+    if (attr.type != hipMemoryTypeDevice || attr.device != B.device)
+        return false;
+    void *base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)p) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return false;
+    }
+    return (const char *)p >= (const char *)base && (const char *)p + bytes <= (const char *)base + size;
+}
+
+template <int W>
+void launch_solve_pack(const val_t *d_rhs, size_t ldb, u32 j0, u32 nc, const SolveWorkspace &ws, const SolveWorkspace::Direction &D)
+{
+    hipLaunchKernelGGL(solve_pack_panel_kernel<W>, dim3(solve_pack_grid((unsigned long long)ws.xlen * W)), dim3(256), 0, B.stream, d_rhs,
+                       (unsigned long long)ldb, j0, nc, D.d_in_idx, D.d_s_in, (u32)ws.n, (unsigned long long)ws.xlen, ws.d_x);
+}
+template <int W>
+void launch_solve_unpack(val_t *d_rhs, size_t ldb, u32 j0, u32 nc, const SolveWorkspace &ws, const SolveWorkspace::Direction &D)
+{
+    hipLaunchKernelGGL(solve_unpack_panel_kernel<W>, dim3(solve_pack_grid((unsigned long long)ws.n * W)), dim3(256), 0, B.stream, d_rhs,
+                       (unsigned long long)ldb, j0, nc, D.d_out_idx, D.d_s_out, (u32)ws.n, ws.d_x);
+}
+// pack (into = true) or unpack a panel of w right-hand sides
+void launch_solve_pack_of(int w, bool into, val_t *d_rhs, size_t ldb, u32 j0, u32 nc, const SolveWorkspace &ws, const SolveWorkspace::Direction &D)
+{
+    switch (w)
+    {
+    case 1:
+        into ? launch_solve_pack<1>(d_rhs, ldb, j0, nc, ws, D) : launch_solve_unpack<1>(d_rhs, ldb, j0, nc, ws, D);
+        break;
+    case 2:
+        into ? launch_solve_pack<2>(d_rhs, ldb, j0, nc, ws, D) : launch_solve_unpack<2>(d_rhs, ldb, j0, nc, ws, D);
+        break;
+    case 4:
+        into ? launch_solve_pack<4>(d_rhs, ldb, j0, nc, ws, D) : launch_solve_unpack<4>(d_rhs, ldb, j0, nc, ws, D);
+        break;
+    case 8:
+        into ? launch_solve_pack<8>(d_rhs, ldb, j0, nc, ws, D) : launch_solve_unpack<8>(d_rhs, ldb, j0, nc, ws, D);
+        break;
+    default:
+        into ? launch_solve_pack<16>(d_rhs, ldb, j0, nc, ws, D) : launch_solve_unpack<16>(d_rhs, ldb, j0, nc, ws, D);
+        break;
+    }
+    HIP_CHECK(hipGetLastError());
 }
 
 const double SV = (double)sizeof(val_t);
@@ -1790,6 +1919,123 @@ extern "C"
 #endif
         block_solve_panels((int)nb, {forward_ut, backward_lt}, {SOLVE_UT | conj, SOLVE_LT | conj}, X, (size_t)xlen, (size_t)npanel, w);
         return wmax;
+    }
+
+    // The same sweeps for right-hand sides that live on the device, on the handle's workspace: per panel pack, both sweeps, unpack, all
+    // on B.stream behind the caller's stream; one synchronisation at the end.
+    int pangulu_platform_0201001_block_trsm_multi_device(pangulu_inblock_idx nb, const pangulu_hip_solve_sweep_t *first,
+                                                         const pangulu_hip_solve_sweep_t *second, int mode, calculate_type *d_rhs,
+                                                         pangulu_uint64_t ldb, pangulu_uint64_t nrhs, pangulu_uint64_t npanel, const int *w,
+                                                         pangulu_uint64_t xlen, const pangulu_hip_solve_maps_t *maps, void **workspace,
+                                                         void *caller_stream)
+    {
+        if (mode < 0 || mode > 2 || (mode != 0 && solve_by_column(nb)))
+            return 0;
+        const int wmax = solve_widest_panel(nb);
+        if (npanel == 0 || nrhs == 0)
+            return wmax;
+        pangulu_uint64_t held = 0;
+        for (size_t p = 0; p < (size_t)npanel; p++)
+        {
+            if (w[p] < 1 || w[p] > wmax || (w[p] & (w[p] - 1)))
+            {
+                fprintf(stderr, "[PanguLU-AMD ERROR] block_trsm_multi_device: panel width %d (nb = %d takes powers of two up to %d)\n", w[p], (int)nb, wmax);
+                exit(EXIT_FAILURE);
+            }
+            held += (pangulu_uint64_t)w[p];
+        }
+        if (held < nrhs || maps->n > xlen || maps->n_user > ldb || !workspace)
+        {
+            fprintf(stderr, "[PanguLU-AMD ERROR] block_trsm_multi_device: panels for %llu of %llu columns, n = %llu, xlen = %llu, ldb = %llu\n",
+                    (unsigned long long)held, (unsigned long long)nrhs, (unsigned long long)maps->n, (unsigned long long)xlen, (unsigned long long)ldb);
+            exit(EXIT_FAILURE);
+        }
+        ensure_ready();
+        std::lock_guard<std::mutex> g(B.mutex);
+        HIP_CHECK(hipSetDevice(B.device));
+        if (!solve_pointer_on_device(d_rhs, sizeof(val_t) * ((size_t)(nrhs - 1) * (size_t)ldb + (size_t)maps->n_user)))
+            return -1;
+        solve_join_factor_streams();
+        SolveWorkspace *ws = (SolveWorkspace *)*workspace;
+        if (ws && (ws->nb != (int)nb || ws->xlen != (size_t)xlen || ws->n != (size_t)maps->n))
+        {
+            solve_workspace_release(ws); // (another system behind the same pointer: start again)
+            ws = nullptr;
+        }
+        if (!ws)
+        {
+            ws = new SolveWorkspace();
+            ws->nb = (int)nb;
+            ws->xlen = (size_t)xlen;
+            ws->n = (size_t)maps->n;
+            solve_workspace_alloc(*ws, &ws->d_x, (size_t)xlen * (size_t)wmax);
+            HIP_CHECK(hipEventCreateWithFlags(&ws->after_caller, hipEventDisableTiming));
+            *workspace = ws;
+        }
+        SolveWorkspace::Direction &D = ws->dir[mode == 0 ? 0 : 1];
+        // (host copies of what goes up: alive until the synchronisation below)
+        std::vector<SolveRowD> hr;
+        std::vector<SolveBlkD> hb;
+        if (!D.ready)
+        {
+            if (mode == 0)
+                build_solve_sweeps({first, second}, {SOLVE_LOWER, SOLVE_UPPER}, hr, hb, D.sweeps);
+            else
+                build_solve_sweeps({first, second}, {SOLVE_UT, SOLVE_LT}, hr, hb, D.sweeps);
+            solve_workspace_alloc(*ws, &D.d_rows, hr.size());
+            solve_workspace_alloc(*ws, &D.d_blks, hb.size());
+            HIP_CHECK(hipMemcpyAsync(D.d_rows, hr.data(), sizeof(SolveRowD) * hr.size(), hipMemcpyHostToDevice, B.stream));
+            HIP_CHECK(hipMemcpyAsync(D.d_blks, hb.data(), sizeof(SolveBlkD) * hb.size(), hipMemcpyHostToDevice, B.stream));
+            const size_t n = ws->n;
+            solve_workspace_alloc(*ws, &D.d_in_idx, n);
+            solve_workspace_alloc(*ws, &D.d_out_idx, n);
+            HIP_CHECK(hipMemcpyAsync(D.d_in_idx, maps->in_idx, sizeof(u32) * n, hipMemcpyHostToDevice, B.stream));
+            HIP_CHECK(hipMemcpyAsync(D.d_out_idx, maps->out_idx, sizeof(u32) * n, hipMemcpyHostToDevice, B.stream));
+            if (maps->s_in)
+            {
+                solve_workspace_alloc(*ws, &D.d_s_in, n);
+                HIP_CHECK(hipMemcpyAsync(D.d_s_in, maps->s_in, sizeof(double) * n, hipMemcpyHostToDevice, B.stream));
+            }
+            if (maps->s_out)
+            {
+                solve_workspace_alloc(*ws, &D.d_s_out, n);
+                HIP_CHECK(hipMemcpyAsync(D.d_s_out, maps->s_out, sizeof(double) * n, hipMemcpyHostToDevice, B.stream));
+            }
+            D.ready = true;
+        }
+#ifdef PANGULU_COMPLEX
+        const int conj = mode == 2 ? SOLVE_CONJ : 0;
+#else
+        const int conj = 0; // (real values: A^H = A^T)
+#endif
+        HIP_CHECK(hipEventRecord(ws->after_caller, (hipStream_t)caller_stream));
+        HIP_CHECK(hipStreamWaitEvent(B.stream, ws->after_caller, 0));
+        u32 j0 = 0;
+        for (size_t p = 0; p < (size_t)npanel && j0 < (u32)nrhs; p++)
+        {
+            const u32 nc = std::min<u32>((u32)w[p], (u32)nrhs - j0);
+            launch_solve_pack_of(w[p], true, d_rhs, (size_t)ldb, j0, nc, *ws, D);
+            launch_solve_panel_of(w[p], (int)nb, D.sweeps, conj, D.d_rows, D.d_blks, ws->d_x);
+            launch_solve_pack_of(w[p], false, d_rhs, (size_t)ldb, j0, nc, *ws, D);
+            j0 += nc;
+        }
+        HIP_CHECK(hipStreamSynchronize(B.stream));
+        return wmax;
+    }
+
+    void pangulu_platform_0201001_solve_workspace_free(void **workspace)
+    {
+        if (!workspace || !*workspace)
+            return;
+        std::lock_guard<std::mutex> g(B.mutex);
+        solve_workspace_release((SolveWorkspace *)*workspace);
+        *workspace = nullptr;
+    }
+
+    unsigned long long pangulu_platform_0201001_get_solve_workspace_bytes(void)
+    {
+        std::lock_guard<std::mutex> g(B.mutex);
+        return (unsigned long long)g_solve_workspace_bytes;
     }
 
     void pangulu_platform_0201001_block_spmv_add(pangulu_inblock_idx nb, pangulu_uint64_t nblk, pangulu_storage_slot_t *const *slots,

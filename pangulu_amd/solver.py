@@ -9,6 +9,7 @@
 implementation: every call goes through the C-ABI of libpangulu_amd_<type>.so.
 """
 import ctypes
+import sys
 
 import numpy as np
 
@@ -101,13 +102,64 @@ def _trans_code(trans):
     return TRANS[trans]
 
 
-_GSTRS_ERRORS = {1: "the handle has not been factorised", 2: "bad rhs / ldb", 3: "unknown trans"}
+_GSTRS_ERRORS = {1: "the handle has not been factorised", 2: "bad rhs / ldb", 3: "unknown trans", 4: "no device-resident path"}
+
+
+def _torch_if_tensor(x):
+    """The torch module if x is a torch.Tensor, else None.  torch is not imported for the question: whoever holds a tensor has
+    imported it already."""
+    if x is None or isinstance(x, (np.ndarray, list, tuple)):
+        return None
+    torch = sys.modules.get("torch")
+    return torch if torch is not None and isinstance(x, torch.Tensor) else None
+
+
+def _gstrs_torch(torch, h, T, code, trans):
+    """pangulu_gstrs / pangulu_gstrs_multi for a torch tensor of shape (n,) or (n, nrhs); returns a new tensor on T's device.
+
+    On the device the factors are on, nothing passes through the host: the columns are solved in place in a column-major copy by
+    pangulu_amd_gstrs_device, ordered behind torch's current stream.  Where that call has no device-resident path for the handle
+    (return code 4) and for a CPU tensor the numpy path runs on a host copy."""
+    want = getattr(torch, np.dtype(h.dtype).name)
+    if T.dtype != want:
+        raise TypeError("the handle solves %s systems, the tensor holds %s" % (want, T.dtype))
+    if T.ndim not in (1, 2) or T.shape[0] != h.n:
+        raise ValueError("a tensor of shape (%d,) or (%d, nrhs) is expected, got %r" % (h.n, h.n, tuple(T.shape)))
+    M = T.detach()
+    M = M.reshape(h.n, 1) if M.ndim == 1 else M
+    nrhs = int(M.shape[1])
+    if M.is_cuda:
+        # column-major with columns h.n apart: one clone() of an input that is laid out that way already, one strided copy otherwise
+        if nrhs > 0 and M.stride() == (1, h.n):
+            X = M.clone()
+        else:
+            X = torch.empty((nrhs, h.n), dtype=want, device=M.device).t()
+            X.copy_(M)
+        opt = _lib.GstrsOptions()
+        with torch.cuda.device(M.device):
+            stream = torch.cuda.current_stream().cuda_stream
+        rc = h.lib.pangulu_amd_gstrs_device(ctypes.c_void_p(X.data_ptr() if nrhs else None), nrhs, h.n, code, ctypes.c_void_p(stream),
+                                            ctypes.byref(opt), h.ref)
+        if rc == 2:
+            raise ValueError("the tensor is on %s, not on the device the factors are on" % (M.device,))
+        if rc not in (0, 4):
+            raise RuntimeError("pangulu_amd_gstrs_device failed (%d): %s" % (rc, _GSTRS_ERRORS.get(rc, "?")))
+        if rc == 4:  # no device-resident path for this handle: through the host
+            X = torch.from_numpy(pangulu_gstrs_multi(h, M.cpu().numpy(), trans=trans)).to(M.device)
+    else:
+        X = torch.from_numpy(pangulu_gstrs_multi(h, M.numpy(), trans=trans))
+    return X.reshape(h.n) if T.ndim == 1 else X
 
 
 def pangulu_gstrs(h, rhs, trans="N"):
     """Solves A x = rhs (trans="N"), A^T x = rhs ("T") or A^H x = rhs ("H") with the factors; returns x (rank 0; other ranks get
-    their input back)."""
+    their input back).  rhs: anything numpy takes, or a torch tensor (see pangulu_gstrs_multi)."""
     code = _trans_code(trans)
+    torch = _torch_if_tensor(rhs)
+    if torch is not None:
+        if rhs.ndim != 1:
+            raise ValueError("rhs must have shape (%d,), got %r" % (h.n, tuple(rhs.shape)))
+        return _gstrs_torch(torch, h, rhs, code, trans)
     opt = _lib.GstrsOptions()
     x = np.array(rhs, dtype=h.dtype, copy=True) if rhs is not None else np.zeros(h.n, dtype=h.dtype)
     if code == 0:
@@ -123,8 +175,17 @@ def pangulu_gstrs_multi(h, B, nrhs=None, trans="N"):
     """Solves A X = B (trans="N"), A^T X = B ("T") or A^H X = B ("H") for all columns of B, shape (n, nrhs) in any memory order, with
     one pass over the factors per panel of columns (pangulu_amd_gstrs_multi / pangulu_amd_gstrs_trans); returns X of the same shape
     (rank 0).  Other ranks pass None and nrhs, and "N" exactly where rank 0 does (it selects the entry point; between "T" and "H"
-    rank 0 decides)."""
+    rank 0 decides).
+
+    B may be a torch tensor of the handle's dtype, shape (n, nrhs) (one rank): the result is a new tensor on the same device and the
+    input is not modified.  A tensor on the device the factors are on is solved there, behind torch's current stream, without a copy
+    to the host (pangulu_amd_gstrs_device; the result is column-major); a CPU tensor takes the numpy path."""
     code = _trans_code(trans)
+    torch = _torch_if_tensor(B)
+    if torch is not None:
+        if B.ndim != 2:
+            raise ValueError("B must have shape (%d, nrhs), got %r" % (h.n, tuple(B.shape)))
+        return _gstrs_torch(torch, h, B, code, trans)
     opt = _lib.GstrsOptions()
     if B is not None:
         B = np.asarray(B)
@@ -276,12 +337,13 @@ def model_for_ranks(h, nranks):
 
 
 def hip_memory(h_or_lib):
-    """Device memory the back-end holds for itself (bytes): mirror pool, descriptor twins of a recorded schedule, GETRF scratch;
-    and the number of blocks in dense mode."""
+    """Device memory the back-end holds for itself (bytes): mirror pool, descriptor twins of a recorded schedule, GETRF scratch,
+    the workspaces of device-resident solves; and the number of blocks in dense mode."""
     lib = h_or_lib.lib if isinstance(h_or_lib, Handle) else h_or_lib
     v = (ctypes.c_ulonglong * 4)()
     lib.pangulu_platform_0201001_get_memory(v)
-    return {"mirror_pool_bytes": int(v[0]), "schedule_descriptor_bytes": int(v[1]), "getrf_scratch_bytes": int(v[2]), "dense_mode_blocks": int(v[3])}
+    return {"mirror_pool_bytes": int(v[0]), "schedule_descriptor_bytes": int(v[1]), "getrf_scratch_bytes": int(v[2]), "dense_mode_blocks": int(v[3]),
+            "solve_workspace_bytes": int(lib.pangulu_platform_0201001_get_solve_workspace_bytes())}
 
 
 def hip_stats(h_or_lib, reset=False):

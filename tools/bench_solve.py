@@ -1,14 +1,18 @@
 """One GPU, one handle: what a block of right-hand sides costs beside single pangulu_gstrs calls on the same factors.
 
-    python tools/bench_solve.py [--matrix elastic3d] [--size 48] [--nb 256] [--vtype r64] [--nrhs 1,4,16,64] [--repeats 5] [--trans N|T|H]
+    python tools/bench_solve.py [--matrix elastic3d] [--size 48] [--nb 256] [--vtype r64] [--nrhs 1,4,16,64] [--repeats 5] [--trans N|T|H] [--device-rhs]
 
 After pangulu_gstrf it times, in this process, the median of `repeats` single pangulu_gstrs calls and the median of `repeats`
 pangulu_gstrs_multi calls per nrhs, and prints one JSON line: the times, the time per column, the panels, the factor bytes a panel
 streams (info.owned_bytes: every record is read once per panel) and the bandwidth that implies.  The yardstick is nrhs single
 calls.  --trans T|H also times the transposed solves (A^T X = B, A^H X = B) of the same handle, the single call and every nrhs, beside
 their untransposed twins: a transposed sweep streams the same factor bytes, so the untransposed time of the same run is its yardstick
-(matrices here are symmetric or nearly so: the residual is that of the transposed system all the same).  (Run it through `tools/gpu_job.sh solve`, which puts it under a time limit.)"""
+(matrices here are symmetric or nearly so: the residual is that of the transposed system all the same).  --device-rhs also times pangulu_amd_gstrs_device
+on a column-major device buffer beside pangulu_amd_gstrs_multi / _trans on a host buffer of the same handle, the raw C calls in place, per nrhs
+(and for --trans): both return synchronised, so a host perf_counter around the call is the time; the host-pointer call is the yardstick and
+its own spread (min .. max of the repeats) the margin.  (Run it through `tools/gpu_job.sh solve`, which puts it under a time limit.)"""
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -31,7 +35,14 @@ def main():
     ap.add_argument("--nrhs", default="1,4,16,64")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--trans", default="N", choices=["N", "T", "H"])
+    ap.add_argument("--device-rhs", action="store_true")
     a = ap.parse_args()
+    if a.device_rhs:
+        # torch brings a HIP runtime of its own under the same soname as the one the library links: a process gets whichever is loaded
+        # first, and torch finds no device on the other one.  So torch first -- as in bench.py and the tests -- and both calls on it.
+        import torch
+
+        torch.cuda.init()
     dt = _lib.VALUE_TYPES[a.vtype][0]
     cplx = np.issubdtype(dt, np.complexfloating)
     if a.matrix == "poisson3d":
@@ -61,6 +72,43 @@ def main():
             f()
             ts.append(time.time() - t)
         return statistics.median(ts)
+
+    def spread_of(f):
+        f()
+        ts = []
+        for _ in range(a.repeats):
+            t = time.perf_counter()
+            f()
+            ts.append(time.perf_counter() - t)
+        return {"median_s": round(statistics.median(ts), 6), "min_s": round(min(ts), 6), "max_s": round(max(ts), 6)}
+
+    def device_beside_host(Bw, trans):
+        """the raw calls, each in place on a buffer of its own (what a buffer holds does not change what a sweep costs)"""
+        import torch
+
+        w, code, opt = Bw.shape[1], {"N": 0, "T": 1, "H": 2}[trans], _lib.GstrsOptions()
+        hbuf = np.array(Bw, order="F", copy=True)
+        dbuf = torch.from_numpy(np.ascontiguousarray(Bw.T)).cuda().t()  # (n, w), column-major
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        hptr, dptr = hbuf.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(dbuf.data_ptr())
+
+        def host_call():
+            assert lib.pangulu_amd_gstrs_trans(hptr, w, n, code, ctypes.byref(opt), h.ref) == 0
+
+        def device_call():
+            assert lib.pangulu_amd_gstrs_device(dptr, w, n, code, stream, ctypes.byref(opt), h.ref) == 0
+
+        hbuf[:] = Bw
+        host_call()
+        Xh = hbuf.copy()
+        device_call()
+        torch.cuda.synchronize()
+        Xd = dbuf.cpu().numpy()
+        path = pa.last_solve_path(h)
+        th, td = spread_of(host_call), spread_of(device_call)
+        return {"trans": trans, "host_pointer": th, "device_pointer": td, "device_vs_host": round(td["median_s"] / th["median_s"], 3),
+                "device_columns": path["device_columns"], "panels": path["panels"],
+                "first_solve_difference": float("%.2e" % (np.abs(Xd - Xh).max() / np.abs(Xh).max()))}
 
     b0 = np.ascontiguousarray(B[:, 0])
     x_single = pa.pangulu_gstrs(h, b0)
@@ -99,6 +147,8 @@ def main():
                                          "panel_width": pt["panel_width"], "panels": pt["panels"],
                                          "implied_gbs": round(pt["panels"] * info["owned_bytes"] / tt / 1e9, 1),
                                          "worst_residual": float("%.2e" % max(trans_residual(Xt[:, j], Bw[:, j]) for j in range(w)))}
+        if a.device_rhs:
+            out["multi"][-1]["device_rhs"] = [device_beside_host(Bw, t) for t in (["N"] if a.trans == "N" else ["N", a.trans])]
     pa.pangulu_finalize(h)
     print(json.dumps(out), flush=True)
 
