@@ -2,7 +2,7 @@
  * solve_mtx.c -- a user program against include/pangulu.h, the way a program written for the reference is
  * (the reference ships examples/example.c:282-300: init, gstrf, gstrs, finalize, then ||Ax - b|| / ||b||).
  *
- *   solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt] [-t]
+ *   solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt] [-t] [-c]
  *
  * Reads a Matrix Market coordinate file (real / integer / pattern, general / symmetric / skew-symmetric) or -- by the last letter of
  * the name, as the reference's example chooses (examples/example.c:100-163) -- its binary .lid layout (u32 rows, u32 columns, u64
@@ -11,6 +11,9 @@
  * examples/example.c:245-266); with it, a text file holding the length on the first non-comment line and one value per line.
  * With -t it then solves the transposed system A^T x = b with the same right-hand side on the same factors
  * (pangulu_amd_gstrs_trans: no second factorisation) and prints || A^T x - b || / || b || as well.
+ * With -c it prints, after the residual, what the factors say about themselves (the factorisation does not pivot): the estimated
+ * reciprocal condition number in the 1-norm (pangulu_amd_rcond), the number of pivots that were clamped and the pivot growth
+ * (pangulu_amd_factor_stats).
  *
  * One process per GPU: started under a launcher that exports RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT (torch.distributed.run does)
  * every process calls pangulu_amd_comm_init() first -- the place of MPI_Init_thread in the reference's example -- and only rank 0
@@ -231,10 +234,12 @@ static void read_vector(const char *path, sparse_index_t n, sparse_value_t *b)
 int main(int argc, char **argv)
 {
     const char *mtx = NULL, *rhs = NULL;
-    int nb = 256, transposed = 0;
+    int nb = 256, transposed = 0, diagnostics = 0;
     for (int a = 1; a < argc; a++)
         if (!strcmp(argv[a], "-t"))
             transposed = 1;
+        else if (!strcmp(argv[a], "-c"))
+            diagnostics = 1;
         else if (!strcmp(argv[a], "-f") && a + 1 < argc)
             mtx = argv[++a];
         else if (!strcmp(argv[a], "-r") && a + 1 < argc)
@@ -242,9 +247,9 @@ int main(int argc, char **argv)
         else if ((!strcmp(argv[a], "-n") || !strcmp(argv[a], "-nb")) && a + 1 < argc)
             nb = atoi(argv[++a]);
         else
-            die("usage: solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt] [-t]", NULL);
+            die("usage: solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt] [-t] [-c]", NULL);
     if (!mtx || nb <= 0)
-        die("usage: solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt] [-t]", NULL);
+        die("usage: solve_mtx -f matrix.mtx|matrix.lid [-n block_order] [-r rhs.txt] [-t] [-c]", NULL);
 
     const int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0;
     const int size = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
@@ -312,6 +317,20 @@ int main(int argc, char **argv)
                (double)info.flop / (t2 - t1) / 1e9, t3 - t2, size);
         printf("|| Ax - b || / || b || = %le\n", sqrt(rr) / sqrt(bb));
         free(ax);
+    }
+    if (diagnostics)
+    {
+        /* both calls are collective; every rank gets the values */
+        double rcond = 0.0;
+        pangulu_amd_factor_stats_t stats;
+        if (pangulu_amd_rcond(PANGULU_AMD_NORM_ONE, &rcond, NULL, NULL, NULL, NULL, &handle) != 0 || pangulu_amd_factor_stats(&handle, &stats) != 0)
+            die("the factor diagnostics failed", NULL);
+        if (rank == 0)
+        {
+            printf("rcond_1 = %le\n", rcond);
+            printf("pivots clamped = %llu\n", stats.clamped_pivots);
+            printf("growth = %le\n", stats.pivot_growth);
+        }
     }
     if (transposed)
     {

@@ -195,6 +195,56 @@ extern "C"
      * (the widest panel; 1: column by column), number of panels.  Any pointer may be NULL.  Returns 0. */
     int pangulu_amd_last_solve_path(void **pangulu_handle, int *device_columns, int *panel_width, int *panels);
 
+    /* ---- factor diagnostics ------------------------------------------------------------------------------ */
+    /* The factorisation does not pivot: a pivot with |Re| < 1e-16 is replaced by 1e-16 wherever it divides, silently, and a matrix
+     * without stored diagonal entries gets 1e-8 ones (info.inserted_diagonals).  These two calls say what that did, from the factors
+     * where they are (nothing is downloaded from a device).
+     *
+     * pangulu_amd_factor_stats: one pass over all stored factor entries.  The stored pivot U(i,i) is the UNCLAMPED value -- every
+     * GETRF path (the per-column kernel, the tiled and the piped blocked kernels, the complex panels) clamps the divisor only -- and
+     * is read where the solves read it: the first entry of its row in the upper diagonal half.  Padding rows of a block-aligned
+     * ordering (unit pivots, info.n_padded > info.n) enter the determinant as exactly 1 and the pivot figures not at all; their unit
+     * entries are among the entries max_abs_u and max_abs_a range over.  The determinant is that of the matrix given to pangulu_init
+     * (the symmetric permutation contributes +1; on a pangulu_amd_set_scaling(1) handle the scalings are divided out and the sign of
+     * the matching is applied), except that with info.inserted_diagonals > 0 it is that of the matrix that was FACTORISED, inserted
+     * diagonals included.  max_abs_a and pivot_growth refer to the factorised matrix as well (the scaled one on a scaling handle).
+     * min_pivot_index is a row of the user's matrix (on a scaling handle its pivot column is the one matched to that row).
+     * Collective like pangulu_amd_factor_check: every rank calls it, every rank gets the values.  Partial results are combined in a
+     * fixed order (no floating-point atomics): the same factors give the same bits.  PANGULU_AMD_DEVICE_SOLVE=0 makes the call
+     * download the factors and walk them on the host, like the solves.  Returns 0, or 1 if the handle has not been factorised (out
+     * untouched). */
+    typedef struct pangulu_amd_factor_stats_t
+    {
+        double det_mantissa_re, det_mantissa_im; /* det(A) = (re + i im) * 2^det_exponent; real types: im = 0 and 0.5 <= |re| < 1;
+                                                    complex: 0.5 <= max(|re|,|im|) < 1; a zero determinant: 0, 0, exponent 0 */
+        long long det_exponent;
+        double log_abs_det;                      /* natural log of |det(A)|; -inf for 0 */
+        double min_abs_pivot, max_abs_pivot;     /* modulus of the stored U(i,i), padding rows excluded */
+        unsigned long long min_pivot_index;      /* row/column of the USER's matrix eliminated at the smallest pivot (first one on a tie) */
+        unsigned long long clamped_pivots;       /* stored pivots with |Re| < 1e-16: the ones factorisation and solves divided by 1e-16 instead */
+        unsigned long long nonfinite_entries;    /* NaN / Inf among all stored factor entries */
+        unsigned long long entries;              /* stored factor entries examined (sum of the records' nnz, all ranks) */
+        double max_abs_l, max_abs_u, max_abs_a;  /* largest modulus in L (unit diagonal not stored), in U, in the matrix that was factorised */
+        double pivot_growth;                     /* max_abs_u / max_abs_a */
+    } pangulu_amd_factor_stats_t;
+    int pangulu_amd_factor_stats(void **pangulu_handle, pangulu_amd_factor_stats_t *out);
+
+    /* An estimate of the reciprocal condition number 1 / (||A|| ||inv(A)||) of the USER's matrix in the 1-norm or the infinity norm.
+     * anorm is the exact norm of the values given to pangulu_init or to the last pangulu_amd_update_values; ainv_norm is Higham's
+     * estimate as LAPACK's xLACN2 makes it (a lower bound, in practice within a factor 3; at most 5 iterations, 11 solves, whatever
+     * the data) from solves with A and A^H on the factors of the last pangulu_gstrf -- permutation, matching and scaling undone by
+     * the solves as in pangulu_amd_gstrs_trans.  On one rank with the factors on the device, where pangulu_amd_gstrs_device offers
+     * both solves, the vectors stay on the device for the whole call and a few scalars come back per step (on_device = 1); otherwise
+     * -- several ranks, PANGULU_AMD_DEVICE_SOLVE=0, PANGULU_HIP_SOLVE_CHUNKED=0 -- the same loop runs on a host vector through the
+     * solves of pangulu_amd_gstrs_multi / _trans.  Nothing in the call is summed by floating-point atomics (on the device its solves
+     * are the reproducible variant of the device-resident solve): the same factors give the same bits.  An infinite ainv_norm gives rcond 0, a NaN in any step rcond NaN.  Every output
+     * pointer may be NULL; solves counts the solves made.  Collective: every rank calls it and gets the values; rank 0's `norm`
+     * decides.  info.time_solve covers the call.  Returns 0; 1 if the handle has not been factorised; 3 for an unknown `norm`
+     * (nothing touched). */
+#define PANGULU_AMD_NORM_ONE 0
+#define PANGULU_AMD_NORM_INF 1
+    int pangulu_amd_rcond(int norm, double *rcond, double *anorm, double *ainv_norm, int *solves, int *on_device, void **pangulu_handle);
+
     /* ---- repeated factorisations (bench.py) ---------------------------------------------------------- */
     /* gstrf overwrites the matrix with its factors.  snapshot() keeps a pristine device-side copy of this rank's
      * block records (call it after pangulu_init, before the first gstrf); reset_numeric() restores the records

@@ -354,6 +354,11 @@ extern "C"
      * Returns the widest panel (npanel = 0 only asks and touches nothing); 0 where the kernels this mode needs are not offered (as
      * block_trsm_multi_trans; nothing is touched); -1 if d_rhs is not device memory of the back-end's device holding ldb x nrhs values
      * (decided on the host from the pointer's attributes, before any launch). */
+    /* `mode` + PANGULU_HIP_SOLVE_REPRODUCIBLE: the same solve with single-vector panels (the widest panel returned is 1) and nothing
+     * summed by atomics -- every block's contribution is stored and the contributions of a segment are added in the order of the
+     * descriptor list -- so that the same factors and the same right-hand side give the same bits from call to call
+     * (pangulu_amd_rcond); twice the launches per level.  0 where that variant is not offered. */
+#define PANGULU_HIP_SOLVE_REPRODUCIBLE 4
     typedef struct pangulu_hip_solve_maps_t
     {
         pangulu_uint64_t n, n_user;
@@ -368,6 +373,58 @@ extern "C"
     void pangulu_platform_0201001_solve_workspace_free(void **workspace);
     /* Device bytes held by all solve workspaces that are alive. */
     unsigned long long pangulu_platform_0201001_get_solve_workspace_bytes(void);
+    /* Optional: statistics of a list of device-resident block records in one launch (one workgroup per record; pangulu_amd_factor_stats).
+     * out[i] describes slots[i]: the entry of largest modulus as its two parts (0, 0 for an empty record; the caller takes the
+     * modulus), the number of NaN / Inf entries and of entries, and -- upper_diag[i] != 0: the record is the upper half of diagonal
+     * block slots[i]->brow_pos, CSR with the pivot first in its row -- over the pivots of the rows r with a stored pivot and
+     * pad[brow_pos * nb + r] == 0: the pivot of smallest modulus (parts, row of the factors' ordering of the first one on a tie;
+     * ~0 when there is none), the one of largest modulus, how many have |Re| < 1e-16, how many there are, and their product as
+     * (prod_re + i prod_im) * 2^prod_exp with 0.5 <= max(|prod_re|, |prod_im|) < 1 (0, 0, 0 for a zero product; the empty product
+     * is 0.5 * 2^1).  `pad` is a HOST array of `xlen` bytes or NULL.  All arithmetic in double; fixed reduction trees, no atomics:
+     * the same records give the same bits.  Returns 0. */
+    typedef struct pangulu_factor_stats_partial_t
+    {
+        double max_re, max_im;
+        unsigned long long nonfinite, entries;
+        double minp_re, minp_im;
+        unsigned long long minp_row;
+        double maxp_re, maxp_im;
+        unsigned long long clamped, pivots;
+        double prod_re, prod_im;
+        long long prod_exp;
+    } pangulu_factor_stats_partial_t;
+    int pangulu_platform_0201001_factor_stats(pangulu_inblock_idx nb, pangulu_uint64_t nblk, pangulu_storage_slot_t *const *slots,
+                                              const int *upper_diag, const unsigned char *pad, pangulu_uint64_t xlen,
+                                              pangulu_factor_stats_partial_t *out);
+    /* Optional: one step between two solves of Higham's 1-norm estimator (pangulu_amd_rcond) on the DEVICE vector d_x of n values,
+     * d_save a second one of the same length (real types: the saved sign vector; may be NULL for complex types):
+     *   PANGULU_CONDEST_FILL_INV_N   x = 1/n
+     *   PANGULU_CONDEST_NORM1_SIGN   norm1 = sum |x_i|, then x = its sign vector (real: +-1; complex: x/|x|, 1 below the smallest
+     *                                normal); real types: unchanged = 1 when `j` != 0 and every sign equals d_save's, d_save = x
+     *   PANGULU_CONDEST_ARGMAX       argmax = first index of the largest |x_i|, absmax = that modulus, abs_prev = |x_j|
+     *   PANGULU_CONDEST_SET_EJ       x = e_j
+     *   PANGULU_CONDEST_FILL_ALT     x_i = (-1)^i (1 + i/(n-1))
+     *   PANGULU_CONDEST_NORM1        norm1 = sum |x_i|
+     * Grid-stride kernels with one partial per workgroup and a last stage by one workgroup, ordered behind `caller_stream` like
+     * block_trsm_multi_device and complete on return; fixed trees, no atomics.  The scratch lives in `*workspace` (the handle's
+     * solve workspace, created here when it is not there yet) and goes with solve_workspace_free.  Steps that reduce fill *out.
+     * Returns 1, 0 for an unknown step, -1 if a vector is not device memory of the back-end's device. */
+#define PANGULU_CONDEST_FILL_INV_N 0
+#define PANGULU_CONDEST_NORM1_SIGN 1
+#define PANGULU_CONDEST_ARGMAX 2
+#define PANGULU_CONDEST_SET_EJ 3
+#define PANGULU_CONDEST_FILL_ALT 4
+#define PANGULU_CONDEST_NORM1 5
+    typedef struct pangulu_condest_result_t
+    {
+        double norm1;
+        double absmax, abs_prev;
+        unsigned long long argmax;
+        unsigned long long unchanged;
+    } pangulu_condest_result_t;
+    int pangulu_platform_0201001_condest_vector(int step, calculate_type *d_x, calculate_type *d_save, pangulu_uint64_t n, pangulu_uint64_t j,
+                                                pangulu_condest_result_t *out, pangulu_inblock_idx nb, pangulu_uint64_t xlen,
+                                                pangulu_uint64_t n_factors, void **workspace, void *caller_stream);
     /* Optional: y[dst segment] += A_blk * x[src segment] for a list of device-resident block records, in one launch (one
      * workgroup per block, floating-point atomics on y).  `x` and `y` are HOST vectors of `xlen` values (nb per block
      * row / column); y is read, updated and written back.  csr[i] != 0: the record is an upper diagonal half (CSR, diagonal

@@ -105,6 +105,33 @@ class Info(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class FactorStats(ctypes.Structure):
+    """pangulu_amd_factor_stats_t (include/pangulu_amd_ext.h)."""
+
+    _fields_ = [
+        ("det_mantissa_re", ctypes.c_double),
+        ("det_mantissa_im", ctypes.c_double),
+        ("det_exponent", ctypes.c_longlong),
+        ("log_abs_det", ctypes.c_double),
+        ("min_abs_pivot", ctypes.c_double),
+        ("max_abs_pivot", ctypes.c_double),
+        ("min_pivot_index", ctypes.c_ulonglong),
+        ("clamped_pivots", ctypes.c_ulonglong),
+        ("nonfinite_entries", ctypes.c_ulonglong),
+        ("entries", ctypes.c_ulonglong),
+        ("max_abs_l", ctypes.c_double),
+        ("max_abs_u", ctypes.c_double),
+        ("max_abs_a", ctypes.c_double),
+        ("pivot_growth", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+NORM_ONE, NORM_INF = 0, 1
+
+
 class HipStats(ctypes.Structure):
     """pangulu_hip_stats_t (include/pangulu_platform.h); class index 1 GETRF, 2 TSTRF, 3 GESSM, 4 SSSSM sparse, 5 SSSSM dense,
     6 densify, 7 sparsify, 8 LU images of remote diagonal blocks."""
@@ -234,6 +261,11 @@ def load(vtype="r64", test_hooks=False):
     lib.pangulu_amd_factor_check.restype = ctypes.c_int
     lib.pangulu_amd_factor_check_vectors.argtypes = [vpp, ctypes.c_int, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_double)]
     lib.pangulu_amd_factor_check_vectors.restype = ctypes.c_int
+    lib.pangulu_amd_factor_stats.argtypes = [vpp, ctypes.POINTER(FactorStats)]
+    lib.pangulu_amd_factor_stats.restype = ctypes.c_int
+    lib.pangulu_amd_rcond.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), vpp]
+    lib.pangulu_amd_rcond.restype = ctypes.c_int
     lib.pangulu_amd_model_for_ranks.argtypes = [vpp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
     lib.pangulu_amd_model_for_ranks.restype = ctypes.c_int
 

@@ -83,6 +83,8 @@ void bind_builtin_hip(Platform &p)
     p.block_trsm_multi_trans = pangulu_platform_0201001_block_trsm_multi_trans;
     p.block_trsm_multi_device = pangulu_platform_0201001_block_trsm_multi_device;
     p.solve_workspace_free = pangulu_platform_0201001_solve_workspace_free;
+    p.factor_stats = pangulu_platform_0201001_factor_stats;
+    p.condest_vector = pangulu_platform_0201001_condest_vector;
     p.block_spmv_add = pangulu_platform_0201001_block_spmv_add;
     p.schedule = pangulu_platform_0201001_schedule;
     p.schedule_range = pangulu_platform_0201001_schedule_range;
@@ -281,6 +283,11 @@ extern "C"
         p.block_trsm_multi_device = (decltype(p.block_trsm_multi_device))dlsym(h, sym);
         snprintf(sym, sizeof(sym), "pangulu_platform_%07x_solve_workspace_free", platform_id);
         p.solve_workspace_free = (decltype(p.solve_workspace_free))dlsym(h, sym);
+        // ... and the factor diagnostics to the host loops of pg_condest.cpp
+        snprintf(sym, sizeof(sym), "pangulu_platform_%07x_factor_stats", platform_id);
+        p.factor_stats = (decltype(p.factor_stats))dlsym(h, sym);
+        snprintf(sym, sizeof(sym), "pangulu_platform_%07x_condest_vector", platform_id);
+        p.condest_vector = (decltype(p.condest_vector))dlsym(h, sym);
         int (*sz)() = (int (*)())dlsym(h, "pangulu_oracle_sizeof_value");
         if (sz && sz() != (int)sizeof(val_t))
         {
@@ -526,6 +533,15 @@ extern "C"
         comm->bcast(A.colptr.data(), sizeof(u64) * A.colptr.size(), 0);
         comm->bcast(A.rowidx.data(), sizeof(u32) * A.rowidx.size(), 0);
         comm->bcast(A.value.data(), sizeof(val_t) * A.value.size(), 0);
+        {
+            // pangulu_amd_rcond's `anorm`: both norms of the values as the user gave them, before scaling or inserted diagonals
+            double norms[2] = {0, 0};
+            if (rank == 0)
+                user_matrix_norms(A.n, A.colptr.data(), A.rowidx.data(), A.value.data(), norms[0], norms[1]);
+            comm->bcast(norms, sizeof(norms), 0);
+            S->user_norm_one = norms[0];
+            S->user_norm_inf = norms[1];
+        }
         S->n_user = A.n;
         S->user_colptr = A.colptr; // (pattern of the matrix as the user passed it: pangulu_amd_update_values maps new values through it)
         S->user_rowidx = A.rowidx;
@@ -1019,6 +1035,51 @@ extern "C"
         return 0;
     }
 
+    int pangulu_amd_factor_stats(void **pangulu_handle, pangulu_amd_factor_stats_t *out)
+    {
+        Solver *S = (Solver *)*pangulu_handle;
+        if (!S->factored)
+            return 1;
+        NearDevice near(active_platform());
+        pangulu_amd_factor_stats_t st;
+        factor_stats(*S, st);
+        if (out)
+            *out = st;
+        return 0;
+    }
+
+    int pangulu_amd_rcond(int norm, double *rcond, double *anorm, double *ainv_norm, int *solves, int *on_device, void **pangulu_handle)
+    {
+        Solver *S = (Solver *)*pangulu_handle;
+        if (!S->factored)
+            return 1;
+        Comm *comm = world();
+        // rank 0's `norm` decides for everybody
+        unsigned long long head[2] = {0, (unsigned long long)(unsigned)norm};
+        if (comm->rank == 0 && norm != PANGULU_AMD_NORM_ONE && norm != PANGULU_AMD_NORM_INF)
+            head[0] = 3;
+        comm->bcast(head, sizeof(head), 0);
+        if (head[0] != 0)
+            return (int)head[0];
+        const double t0 = wall_seconds();
+        NearDevice near(active_platform());
+        double rc = 0, an = 0, ai = 0;
+        int ns = 0, dev = 0;
+        reciprocal_condition(*S, (int)head[1], rc, an, ai, ns, dev);
+        S->info.time_solve = wall_seconds() - t0;
+        if (rcond)
+            *rcond = rc;
+        if (anorm)
+            *anorm = an;
+        if (ainv_norm)
+            *ainv_norm = ai;
+        if (solves)
+            *solves = ns;
+        if (on_device)
+            *on_device = dev;
+        return 0;
+    }
+
     int pangulu_amd_update_values(void **pangulu_handle, const sparse_value_t *csc_value)
     {
         Solver *S = (Solver *)*pangulu_handle;
@@ -1035,6 +1096,7 @@ extern "C"
         // by row, so locate each entry by binary search
         if (S->user_colptr.size() != (size_t)S->n_user + 1)
             return 2;
+        user_matrix_norms(S->n_user, S->user_colptr.data(), S->user_rowidx.data(), vals.data(), S->user_norm_one, S->user_norm_inf);
         CscMatrix &B = S->Aperm;
 #pragma omp parallel for schedule(dynamic, 512)
         for (i64 j_ = 0; j_ < (i64)S->n_user; j_++)

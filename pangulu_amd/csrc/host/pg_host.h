@@ -92,6 +92,12 @@ struct Platform
                                    pangulu_uint64_t, pangulu_uint64_t, pangulu_uint64_t, const int *, pangulu_uint64_t,
                                    const pangulu_hip_solve_maps_t *, void **, void *) = nullptr;
     void (*solve_workspace_free)(void **) = nullptr;
+    // optional: statistics of device-resident records in one launch, and the estimator's steps between two solves on a device vector
+    // (pangulu_amd_factor_stats / pangulu_amd_rcond); a platform without them gets the host loops of pg_condest.cpp
+    int (*factor_stats)(pangulu_inblock_idx, pangulu_uint64_t, slot_t *const *, const int *, const unsigned char *, pangulu_uint64_t,
+                        pangulu_factor_stats_partial_t *) = nullptr;
+    int (*condest_vector)(int, val_t *, val_t *, pangulu_uint64_t, pangulu_uint64_t, pangulu_condest_result_t *, pangulu_inblock_idx, pangulu_uint64_t,
+                          pangulu_uint64_t, void **, void *) = nullptr;
 };
 Platform &active_platform();               // built-in HIP unless the test hook replaced it
 bool platform_is_builtin_hip();
@@ -358,6 +364,9 @@ struct Solver
     CscMatrix Aperm;                       // kept for the factor check and residuals (rank 0 / all ranks)
     std::vector<u64> user_colptr;          // pattern of the user's matrix (for pangulu_amd_update_values)
     std::vector<u32> user_rowidx;
+    // 1-norm and infinity-norm of the values given to pangulu_init or the last pangulu_amd_update_values (rank 0 computes, everyone
+    // holds them): pangulu_amd_rcond's `anorm`; the values themselves are not kept
+    double user_norm_one = 0, user_norm_inf = 0;
     // numeric state
     Storage storage;
     std::vector<slot_t *> slot_of;         // per non-diagonal block: owned / received slot, nullptr otherwise
@@ -479,8 +488,15 @@ void triangular_solve_multi_trans(Solver &S, val_t *B, u32 nrhs, bool conjugate)
 const SolveMaps &solve_maps(Solver &S, bool transposed);  // pg_api.cpp: the handle's maps for a direction, built on first use (rank 0)
 // The same solves for an ldb x nrhs column-major matrix in DEVICE memory, in and out of factor space on the device through solve_maps(),
 // ordered behind `stream` (one rank).  0: done; 2: the back-end refused the pointer; 4: no device-resident path for this handle (nothing touched)
-int triangular_solve_device(Solver &S, val_t *d_rhs, u32 nrhs, u64 ldb, int trans, void *stream);
+// reproducible: single-vector panels and no sums by atomics -- the same bits from call to call (pangulu_amd_rcond); 4 where the back-end lacks it
+int triangular_solve_device(Solver &S, val_t *d_rhs, u32 nrhs, u64 ldb, int trans, void *stream, bool reproducible = false);
+bool device_solve_offered(Solver &S, int trans, bool reproducible = false); // triangular_solve_device would not return 4 for this direction (nothing touched)
 void drop_solve_workspace(Solver &S);                     // before the factors change, and when the handle goes
+// pg_condest.cpp: what pangulu_amd_factor_stats and pangulu_amd_rcond do (collective)
+void user_matrix_norms(u32 n, const u64 *colptr, const u32 *rowidx, const val_t *value, double &norm_one, double &norm_inf);
+void factor_stats(Solver &S, pangulu_amd_factor_stats_t &out);
+// norm: PANGULU_AMD_NORM_ONE / _INF.  A NaN in any step gives NaN, an infinite estimate 0; always terminates (at most 11 solves)
+void reciprocal_condition(Solver &S, int norm, double &rcond, double &anorm, double &ainv_norm, int &solves, int &on_device);
 double factor_check(Solver &S);                           // ||L(U 1) - A 1|| / ||A 1|| on the factors where they are (pg_check.cpp; collective)
 double factor_check_vectors(Solver &S, int nvec, unsigned long long seed); // the same on the ones vector + nvec - 1 random +-1 vectors: the worst quotient
 void compute_task_model(Solver &S, double hbm_bytes_per_s, double fp_flops_per_s); // pg_model.cpp: T* of SURVEY.md §8d

@@ -522,13 +522,25 @@ void triangular_solve_multi_trans(Solver &S, val_t *Bm, u32 nrhs, bool conjugate
 // pangulu_amd_gstrs_device: the columns of a device matrix through Platform::block_trsm_multi_device, which packs, sweeps and unpacks
 // each panel on the device and keeps what does not depend on the right-hand sides in S.solve_workspace.  Every condition for 4 is
 // this rank's own (no exchange), and nothing has been touched when it is returned.
-int triangular_solve_device(Solver &S, val_t *d_rhs, u32 nrhs, u64 ldb, int trans, void *stream)
+// the widest panel the device-resident solve of this direction takes; 0: no such path for this handle
+static int device_solve_widest_panel(Solver &S, int trans, bool reproducible)
 {
     Platform &plat = active_platform();
     if (!device_solve_enabled(S, plat) || !plat.block_trsm_multi_device || !plat.solve_workspace_free)
-        return 4;
+        return 0;
     const pangulu_uint64_t xlen = (pangulu_uint64_t)S.nbk * S.nb;
-    const int wmax = plat.block_trsm_multi_device((pangulu_inblock_idx)S.nb, nullptr, nullptr, trans, nullptr, 0, 0, 0, nullptr, xlen, nullptr, nullptr, nullptr);
+    const int wmax = plat.block_trsm_multi_device((pangulu_inblock_idx)S.nb, nullptr, nullptr, trans | (reproducible ? PANGULU_HIP_SOLVE_REPRODUCIBLE : 0), nullptr,
+                                                  0, 0, 0, nullptr, xlen, nullptr, nullptr, nullptr);
+    return wmax < 1 ? 0 : wmax;
+}
+
+bool device_solve_offered(Solver &S, int trans, bool reproducible) { return device_solve_widest_panel(S, trans, reproducible) > 0; }
+
+int triangular_solve_device(Solver &S, val_t *d_rhs, u32 nrhs, u64 ldb, int trans, void *stream, bool reproducible)
+{
+    Platform &plat = active_platform();
+    const pangulu_uint64_t xlen = (pangulu_uint64_t)S.nbk * S.nb;
+    const int wmax = device_solve_widest_panel(S, trans, reproducible);
     if (wmax < 1)
         return 4;
     const SolveMaps &M = solve_maps(S, trans != PANGULU_AMD_TRANS_NONE);
@@ -542,7 +554,7 @@ int triangular_solve_device(Solver &S, val_t *d_rhs, u32 nrhs, u64 ldb, int tran
     pangulu_hip_solve_sweep_t sw[2];
     solve_sweeps_of(S, trans, sw);
     const std::vector<int> w = solve_panel_widths(nrhs, wmax);
-    const int rc = plat.block_trsm_multi_device((pangulu_inblock_idx)S.nb, &sw[0], &sw[1], trans, d_rhs, ldb, nrhs, (pangulu_uint64_t)w.size(), w.data(), xlen,
+    const int rc = plat.block_trsm_multi_device((pangulu_inblock_idx)S.nb, &sw[0], &sw[1], trans | (reproducible ? PANGULU_HIP_SOLVE_REPRODUCIBLE : 0), d_rhs, ldb, nrhs, (pangulu_uint64_t)w.size(), w.data(), xlen,
                                                 &maps, &S.solve_workspace, stream);
     if (rc < 0)
         return 2;

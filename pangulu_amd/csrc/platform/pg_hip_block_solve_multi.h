@@ -178,6 +178,103 @@ __global__ __launch_bounds__(256) void block_trsm_gather_trans_kernel(const Solv
     }
 }
 
+// -----------------------------------------------------------------------------------------------------------------
+// The REPRODUCIBLE gather for single vectors (pangulu_amd_rcond: the same factors and the same vector must give the same bits).  The
+// two kernels above leave the order of their sums to the hardware: LDS atomics inside a block, one global atomic per block and row
+// across the blocks of a segment.  Here nothing is added by an atomic:
+//  * solve_gather_part_kernel, one workgroup per block: the block's contribution -B x_src (or -op(B)^T x_src) as nb values of its own
+//    in `part`, every one of them written.  Transposed: the lane groups' dots of the kernel above, stored instead of added.
+//    Untransposed: a scatter -- wavefront w takes the columns c = w, w + 4, ... one after the other into a tile of its own (the entries
+//    of one column go to distinct rows: plain read-modify-write, columns in ascending order), and the four tiles are added in
+//    wavefront order;
+//  * solve_gather_sum_kernel, one workgroup per segment of the level: x_row += part of its blocks, in the order of the descriptor list.
+// The level kernel that follows sweeps a diagonal half with one wavefront and shuffle sums in a fixed pattern: reproducible as it is.
+// Twice the launches of the atomic pair and nb values of traffic per block each way: only where reproducibility is asked for.
+// -----------------------------------------------------------------------------------------------------------------
+inline size_t solve_repro_lds_gather(size_t nb) { return 5 * sizeof(val_t) * nb + sizeof(u32) * (nb + 1); }
+
+template <bool TRANS, bool CONJ>
+__global__ __launch_bounds__(256) void solve_gather_part_kernel(const SolveBlkD *__restrict__ blks, int nb, const val_t *__restrict__ x,
+                                                                val_t *__restrict__ part)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    val_t *xs = reinterpret_cast<val_t *>(smem_raw);
+    val_t *acc = xs + nb; // untransposed: four tiles of nb values
+    u32 *cp = reinterpret_cast<u32 *>(xs + (size_t)5 * nb);
+    const SolveBlkD B = blks[blockIdx.x];
+    const val_t *xsrc = x + (size_t)B.bcol * nb;
+    val_t *out = part + (size_t)blockIdx.x * nb;
+    const int tid = threadIdx.x;
+    for (int k = tid; k < nb; k += 256)
+        xs[k] = xsrc[k];
+    for (int i = tid; i <= nb; i += 256)
+        cp[i] = i == 0 ? 0u : B.cp[i];
+    if constexpr (!TRANS)
+        for (int k = tid; k < 4 * nb; k += 256)
+            acc[k] = v_make(0);
+    __syncthreads();
+    if constexpr (TRANS)
+    {
+        const int g = solve_trans_group_slots(cp[nb], nb, 1); // uniform over the workgroup
+        const int ngroup = 256 / g;
+        const int group = tid / g, slot = tid % g;
+        for (int c0 = 0; c0 < nb; c0 += ngroup) // (uniform trip count: the shuffles below are executed by whole wavefronts)
+        {
+            const int c = c0 + group;
+            val_t sum = v_make(0);
+            u32 p0 = 0, p1 = 0;
+            if (c < nb)
+            {
+                p0 = cp[c];
+                p1 = cp[c + 1];
+            }
+            for (u32 p = p0 + (u32)slot; p < p1; p += (u32)g)
+                sum = v_add(sum, v_mul(solve_trans_op<CONJ>(B.val[p]), xs[B.ri[p]]));
+            sum = solve_group_sum<1>(sum, g);
+            if (slot == 0 && c < nb)
+                out[c] = v_sub(v_make(0), sum);
+        }
+    }
+    else
+    {
+        const int wave = tid >> 6, lane = tid & 63;
+        val_t *mine = acc + (size_t)wave * nb;
+        for (int c = wave; c < nb; c += 4)
+        {
+            const u32 p0 = cp[c], p1 = cp[c + 1];
+            if (p0 == p1)
+                continue; // (uniform over the wavefront)
+            const val_t xc = xs[c];
+            for (u32 p = p0 + (u32)lane; p < p1; p += 64)
+            {
+                val_t *d = &mine[B.ri[p]];
+                *d = v_submul(*d, B.val[p], xc);
+            }
+            wave_lds_fence();
+        }
+        __syncthreads();
+        for (int i = tid; i < nb; i += 256)
+            out[i] = v_add(v_add(v_add(acc[i], acc[nb + i]), acc[2 * nb + i]), acc[3 * nb + i]);
+    }
+}
+
+// rows[blockIdx.x].first counts from the sweep's first block, `level_first` is the level's first block counted the same way, and
+// `part` holds the level's blocks from 0
+__global__ __launch_bounds__(256) void solve_gather_sum_kernel(const SolveRowD *__restrict__ rows, unsigned long long level_first, int nb,
+                                                               const val_t *__restrict__ part, val_t *__restrict__ x)
+{
+    const SolveRowD R = rows[blockIdx.x];
+    val_t *xr = x + (size_t)R.brow * nb;
+    const val_t *first = part + (size_t)(R.first - level_first) * nb;
+    for (int i = threadIdx.x; i < nb; i += 256)
+    {
+        val_t s = xr[i];
+        for (u32 b = 0; b < R.nblk; b++)
+            s = v_add(s, first[(size_t)b * nb + i]);
+        xr[i] = s;
+    }
+}
+
 // One record of a diagonal half out of its chunk in LDS (the table above), by the sweeping wavefront: record c is bv / bi[ptr[c] - base
 // .. ptr[c + 1] - base), lane = entry slot `eslot` x right-hand side `r`.  (A function of values, not a lambda over the kernel's
 // locals: the compiler then keeps what does not depend on c out of the record loop, as it did in a loop written out per sweep.)

@@ -894,11 +894,25 @@ void solve_allow_lds(size_t lds)
 }
 
 // one level of one sweep on a panel of W right-hand sides: the gather over the level's nbl blocks, then the diagonal halves of its n segments
+// repro_part (single vectors only): the reproducible gather pair into that buffer of nbl x nb values instead of the atomic gather;
+// level_first: the level's first block counted from the sweep's first
 template <int SWEEP, int W, bool CONJ>
-void launch_solve_level_as(int nb, int ch, size_t nbl, size_t n, const SolveBlkD *blks, const SolveRowD *rows, val_t *d_x)
+void launch_solve_level_as(int nb, int ch, size_t nbl, size_t n, const SolveBlkD *blks, const SolveRowD *rows, val_t *d_x, val_t *repro_part = nullptr,
+                           size_t level_first = 0)
 {
     const size_t lds_level = solve_multi_lds_level((size_t)nb, W, ch);
-    if constexpr (solve_sweep_transposed(SWEEP))
+    if (W == 1 && repro_part)
+    {
+        constexpr bool TRANS = solve_sweep_transposed(SWEEP);
+        const size_t lds_gather = solve_repro_lds_gather((size_t)nb);
+        solve_allow_lds<solve_gather_part_kernel<TRANS, CONJ>>(lds_gather);
+        if (nbl)
+        {
+            hipLaunchKernelGGL((solve_gather_part_kernel<TRANS, CONJ>), dim3((unsigned)nbl), dim3(256), lds_gather, B.stream, blks, nb, d_x, repro_part);
+            hipLaunchKernelGGL(solve_gather_sum_kernel, dim3((unsigned)n), dim3(256), 0, B.stream, rows, (unsigned long long)level_first, nb, repro_part, d_x);
+        }
+    }
+    else if constexpr (solve_sweep_transposed(SWEEP))
     {
         const size_t lds_gather = solve_trans_lds_gather((size_t)nb, W);
         solve_allow_lds<block_trsm_gather_trans_kernel<W, CONJ>>(lds_gather);
@@ -919,7 +933,8 @@ void launch_solve_level_as(int nb, int ch, size_t nbl, size_t n, const SolveBlkD
 // the same for a run-time mode.  by_column: the column-by-column pair of pg_hip_block_solve.h (single vectors, untransposed sweeps: the
 // operator offers no transposed sweep where that pair would run)
 template <int W>
-void launch_solve_level(int mode, bool by_column, int nb, int ch, size_t nbl, size_t n, const SolveBlkD *blks, const SolveRowD *rows, val_t *d_x)
+void launch_solve_level(int mode, bool by_column, int nb, int ch, size_t nbl, size_t n, const SolveBlkD *blks, const SolveRowD *rows, val_t *d_x,
+                        val_t *repro_part = nullptr, size_t level_first = 0)
 {
     if (by_column)
     {
@@ -935,25 +950,26 @@ void launch_solve_level(int mode, bool by_column, int nb, int ch, size_t nbl, si
     switch (mode)
     {
     case SOLVE_LOWER:
-        return launch_solve_level_as<SOLVE_LOWER, W, false>(nb, ch, nbl, n, blks, rows, d_x);
+        return launch_solve_level_as<SOLVE_LOWER, W, false>(nb, ch, nbl, n, blks, rows, d_x, repro_part, level_first);
     case SOLVE_UPPER:
-        return launch_solve_level_as<SOLVE_UPPER, W, false>(nb, ch, nbl, n, blks, rows, d_x);
+        return launch_solve_level_as<SOLVE_UPPER, W, false>(nb, ch, nbl, n, blks, rows, d_x, repro_part, level_first);
     case SOLVE_UT:
-        return launch_solve_level_as<SOLVE_UT, W, false>(nb, ch, nbl, n, blks, rows, d_x);
+        return launch_solve_level_as<SOLVE_UT, W, false>(nb, ch, nbl, n, blks, rows, d_x, repro_part, level_first);
     case SOLVE_LT:
-        return launch_solve_level_as<SOLVE_LT, W, false>(nb, ch, nbl, n, blks, rows, d_x);
+        return launch_solve_level_as<SOLVE_LT, W, false>(nb, ch, nbl, n, blks, rows, d_x, repro_part, level_first);
 #ifdef PANGULU_COMPLEX // (real builds: A^H is A^T, the operator never adds SOLVE_CONJ)
     case SOLVE_UT | SOLVE_CONJ:
-        return launch_solve_level_as<SOLVE_UT, W, true>(nb, ch, nbl, n, blks, rows, d_x);
+        return launch_solve_level_as<SOLVE_UT, W, true>(nb, ch, nbl, n, blks, rows, d_x, repro_part, level_first);
     case SOLVE_LT | SOLVE_CONJ:
-        return launch_solve_level_as<SOLVE_LT, W, true>(nb, ch, nbl, n, blks, rows, d_x);
+        return launch_solve_level_as<SOLVE_LT, W, true>(nb, ch, nbl, n, blks, rows, d_x, repro_part, level_first);
 #endif
     }
 }
 
 // the launches of one panel of W right-hand sides in d_x: the sweeps one after the other, a gather and a level launch per level
 template <int W>
-void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, int conj, const SolveRowD *d_rows, const SolveBlkD *d_blks, val_t *d_x)
+void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, int conj, const SolveRowD *d_rows, const SolveBlkD *d_blks, val_t *d_x,
+                        val_t *repro_part = nullptr)
 {
     const bool by_column = W == 1 && solve_by_column((size_t)nb);
     const int ch = by_column ? 0 : solve_multi_chunk((size_t)nb, W, SOLVE_LDS_BUDGET);
@@ -966,17 +982,18 @@ void launch_solve_panel(int nb, const std::vector<SolveSweepD> &sweeps, int conj
                 continue;
             const SolveBlkD *blks = d_blks + S.blk0 + S.blk_level_ptr[l];
             const SolveRowD *rows = d_rows + S.row0 + lp[l];
-            launch_solve_level<W>(S.mode | conj, by_column, nb, ch, nbl, n, blks, rows, d_x);
+            launch_solve_level<W>(S.mode | conj, by_column, nb, ch, nbl, n, blks, rows, d_x, repro_part, S.blk_level_ptr[l]);
         }
 }
 
 // ... of a panel of w right-hand sides, w a width solve_widest_panel() allows.  conj: SOLVE_CONJ on top of the sweeps' (transposed) modes, or 0
-void launch_solve_panel_of(int w, int nb, const std::vector<SolveSweepD> &sweeps, int conj, const SolveRowD *d_rows, const SolveBlkD *d_blks, val_t *d_x)
+void launch_solve_panel_of(int w, int nb, const std::vector<SolveSweepD> &sweeps, int conj, const SolveRowD *d_rows, const SolveBlkD *d_blks, val_t *d_x,
+                           val_t *repro_part = nullptr)
 {
     switch (w)
     {
     case 1:
-        launch_solve_panel<1>(nb, sweeps, conj, d_rows, d_blks, d_x);
+        launch_solve_panel<1>(nb, sweeps, conj, d_rows, d_blks, d_x, repro_part);
         break;
     case 2:
         launch_solve_panel<2>(nb, sweeps, conj, d_rows, d_blks, d_x);
@@ -1061,6 +1078,7 @@ void block_solve_panels(int nb, const std::vector<const pangulu_hip_solve_sweep_
 }
 
 #include "pg_hip_solve_pack.h"
+#include "pg_hip_factor_stats.h"
 
 // What a handle's device-resident solves keep on the device between calls (pangulu_platform_0201001_block_trsm_multi_device): per
 // direction ([0] A, [1] A^T and A^H) the descriptors of both sweeps and the index/scale maps, each built on first use, and one panel
@@ -1079,6 +1097,12 @@ struct SolveWorkspace
     int nb = 0;
     size_t xlen = 0, n = 0;
     val_t *d_x = nullptr; // xlen x the widest panel
+    // pangulu_platform_0201001_condest_vector: the workgroups' partials and the result of a step
+    CondestPartialD *d_condest_part = nullptr;
+    CondestResultD *d_condest_res = nullptr;
+    // the reproducible single-vector solve: one nb-vector per block of the fullest level
+    val_t *d_repro_part = nullptr;
+    size_t repro_part_values = 0;
     hipEvent_t after_caller = nullptr;
     size_t bytes = 0;
 };
@@ -1100,12 +1124,35 @@ void solve_workspace_release(SolveWorkspace *ws) // B.mutex held
         for (void *p : {(void *)D.d_rows, (void *)D.d_blks, (void *)D.d_in_idx, (void *)D.d_out_idx, (void *)D.d_s_in, (void *)D.d_s_out})
             if (p)
                 HIP_CHECK(hipFree(p));
-    if (ws->d_x)
-        HIP_CHECK(hipFree(ws->d_x));
+    for (void *p : {(void *)ws->d_x, (void *)ws->d_condest_part, (void *)ws->d_condest_res, (void *)ws->d_repro_part})
+        if (p)
+            HIP_CHECK(hipFree(p));
     if (ws->after_caller)
         HIP_CHECK(hipEventDestroy(ws->after_caller));
     g_solve_workspace_bytes -= ws->bytes;
     delete ws;
+}
+
+// the handle's workspace for a system of these sizes, made when it is not there (B.mutex held)
+SolveWorkspace *solve_workspace_of(void **workspace, int nb, size_t xlen, size_t n)
+{
+    SolveWorkspace *ws = (SolveWorkspace *)*workspace;
+    if (ws && (ws->nb != nb || ws->xlen != xlen || ws->n != n))
+    {
+        solve_workspace_release(ws); // (another system behind the same pointer: start again)
+        ws = nullptr;
+    }
+    if (!ws)
+    {
+        ws = new SolveWorkspace();
+        ws->nb = nb;
+        ws->xlen = xlen;
+        ws->n = n;
+        solve_workspace_alloc(*ws, &ws->d_x, xlen * (size_t)solve_widest_panel((size_t)nb));
+        HIP_CHECK(hipEventCreateWithFlags(&ws->after_caller, hipEventDisableTiming));
+        *workspace = ws;
+    }
+    return ws;
 }
 
 // true: [p, p + bytes) is device memory of the back-end's device.  Asked of the runtime on the host: no kernel sees a pointer that fails.
@@ -1929,9 +1976,15 @@ extern "C"
                                                          pangulu_uint64_t xlen, const pangulu_hip_solve_maps_t *maps, void **workspace,
                                                          void *caller_stream)
     {
+        // (the reproducible variant is built on the chunked level kernel and takes single vectors)
+        const bool repro = mode >= 0 && (mode & PANGULU_HIP_SOLVE_REPRODUCIBLE) != 0;
+        if (repro)
+            mode &= ~PANGULU_HIP_SOLVE_REPRODUCIBLE;
         if (mode < 0 || mode > 2 || (mode != 0 && solve_by_column(nb)))
             return 0;
-        const int wmax = solve_widest_panel(nb);
+        if (repro && (solve_by_column(nb) || solve_repro_lds_gather(nb) > SOLVE_LDS_BUDGET))
+            return 0;
+        const int wmax = repro ? 1 : solve_widest_panel(nb);
         if (npanel == 0 || nrhs == 0)
             return wmax;
         pangulu_uint64_t held = 0;
@@ -1956,22 +2009,7 @@ extern "C"
         if (!solve_pointer_on_device(d_rhs, sizeof(val_t) * ((size_t)(nrhs - 1) * (size_t)ldb + (size_t)maps->n_user)))
             return -1;
         solve_join_factor_streams();
-        SolveWorkspace *ws = (SolveWorkspace *)*workspace;
-        if (ws && (ws->nb != (int)nb || ws->xlen != (size_t)xlen || ws->n != (size_t)maps->n))
-        {
-            solve_workspace_release(ws); // (another system behind the same pointer: start again)
-            ws = nullptr;
-        }
-        if (!ws)
-        {
-            ws = new SolveWorkspace();
-            ws->nb = (int)nb;
-            ws->xlen = (size_t)xlen;
-            ws->n = (size_t)maps->n;
-            solve_workspace_alloc(*ws, &ws->d_x, (size_t)xlen * (size_t)wmax);
-            HIP_CHECK(hipEventCreateWithFlags(&ws->after_caller, hipEventDisableTiming));
-            *workspace = ws;
-        }
+        SolveWorkspace *ws = solve_workspace_of(workspace, (int)nb, (size_t)xlen, (size_t)maps->n);
         SolveWorkspace::Direction &D = ws->dir[mode == 0 ? 0 : 1];
         // (host copies of what goes up: alive until the synchronisation below)
         std::vector<SolveRowD> hr;
@@ -2008,6 +2046,26 @@ extern "C"
 #else
         const int conj = 0; // (real values: A^H = A^T)
 #endif
+        if (repro)
+        {
+            size_t fullest = 1;
+            for (const SolveSweepD &S : D.sweeps)
+                for (size_t l = 0; l + 1 < S.blk_level_ptr.size(); l++)
+                    fullest = std::max(fullest, S.blk_level_ptr[l + 1] - S.blk_level_ptr[l]);
+            if (fullest * (size_t)nb > ws->repro_part_values)
+            {
+                if (ws->d_repro_part)
+                {
+                    HIP_CHECK(hipStreamSynchronize(B.stream));
+                    HIP_CHECK(hipFree(ws->d_repro_part));
+                    ws->bytes -= sizeof(val_t) * ws->repro_part_values;
+                    g_solve_workspace_bytes -= sizeof(val_t) * ws->repro_part_values;
+                    ws->d_repro_part = nullptr;
+                }
+                ws->repro_part_values = fullest * (size_t)nb;
+                solve_workspace_alloc(*ws, &ws->d_repro_part, ws->repro_part_values);
+            }
+        }
         HIP_CHECK(hipEventRecord(ws->after_caller, (hipStream_t)caller_stream));
         HIP_CHECK(hipStreamWaitEvent(B.stream, ws->after_caller, 0));
         u32 j0 = 0;
@@ -2015,7 +2073,7 @@ extern "C"
         {
             const u32 nc = std::min<u32>((u32)w[p], (u32)nrhs - j0);
             launch_solve_pack_of(w[p], true, d_rhs, (size_t)ldb, j0, nc, *ws, D);
-            launch_solve_panel_of(w[p], (int)nb, D.sweeps, conj, D.d_rows, D.d_blks, ws->d_x);
+            launch_solve_panel_of(w[p], (int)nb, D.sweeps, conj, D.d_rows, D.d_blks, ws->d_x, repro ? ws->d_repro_part : nullptr);
             launch_solve_pack_of(w[p], false, d_rhs, (size_t)ldb, j0, nc, *ws, D);
             j0 += nc;
         }
@@ -2036,6 +2094,112 @@ extern "C"
     {
         std::lock_guard<std::mutex> g(B.mutex);
         return (unsigned long long)g_solve_workspace_bytes;
+    }
+
+    // One launch over the listed records (pg_hip_factor_stats.h): descriptors and the padding mask up, one partial per record back.
+    int pangulu_platform_0201001_factor_stats(pangulu_inblock_idx nb, pangulu_uint64_t nblk, pangulu_storage_slot_t *const *slots,
+                                              const int *upper_diag, const unsigned char *pad, pangulu_uint64_t xlen,
+                                              pangulu_factor_stats_partial_t *out)
+    {
+        static_assert(sizeof(FactorStatsPartialD) == sizeof(pangulu_factor_stats_partial_t), "the kernel's partial is the operator's");
+        if (nblk == 0)
+            return 0;
+        ensure_ready();
+        std::lock_guard<std::mutex> g(B.mutex);
+        solve_join_factor_streams();
+        std::vector<FactorStatsBlkD> hb((size_t)nblk);
+        for (size_t i = 0; i < (size_t)nblk; i++)
+        {
+            const slot_t *s = slots[i];
+            hb[i].val = s->d_value;
+            hb[i].rowptr = upper_diag[i] ? s->d_rowpointer : nullptr;
+            hb[i].nnz = s->columnpointer[nb]; // (the pattern's host copy is always current)
+            hb[i].row0 = (unsigned long long)s->brow_pos * nb;
+            if (upper_diag[i] && hb[i].row0 + nb > xlen)
+            {
+                fprintf(stderr, "[PanguLU-AMD ERROR] factor_stats: diagonal block %u of order %d outside %llu rows\n", (unsigned)s->brow_pos, (int)nb,
+                        (unsigned long long)xlen);
+                exit(EXIT_FAILURE);
+            }
+        }
+        FactorStatsBlkD *d_blks = nullptr;
+        FactorStatsPartialD *d_out = nullptr;
+        unsigned char *d_pad = nullptr;
+        HIP_CHECK(hipMalloc((void **)&d_blks, sizeof(FactorStatsBlkD) * hb.size()));
+        HIP_CHECK(hipMalloc((void **)&d_out, sizeof(FactorStatsPartialD) * hb.size()));
+        HIP_CHECK(hipMemcpyAsync(d_blks, hb.data(), sizeof(FactorStatsBlkD) * hb.size(), hipMemcpyHostToDevice, B.stream));
+        if (pad)
+        {
+            HIP_CHECK(hipMalloc((void **)&d_pad, (size_t)xlen));
+            HIP_CHECK(hipMemcpyAsync(d_pad, pad, (size_t)xlen, hipMemcpyHostToDevice, B.stream));
+        }
+        hipLaunchKernelGGL(factor_stats_kernel, dim3((unsigned)nblk), dim3(FS_THREADS), 4 * sizeof(FsMax), B.stream, d_blks, (int)nb, d_pad, d_out);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(FactorStatsPartialD) * hb.size(), hipMemcpyDeviceToHost, B.stream));
+        HIP_CHECK(hipStreamSynchronize(B.stream));
+        HIP_CHECK(hipFree(d_blks));
+        HIP_CHECK(hipFree(d_out));
+        if (d_pad)
+            HIP_CHECK(hipFree(d_pad));
+        return 0;
+    }
+
+    // One step of the estimator between two solves, on B.stream behind the caller's stream; the result comes back in one small copy.
+    int pangulu_platform_0201001_condest_vector(int step, calculate_type *d_x, calculate_type *d_save, pangulu_uint64_t n, pangulu_uint64_t j,
+                                                pangulu_condest_result_t *out, pangulu_inblock_idx nb, pangulu_uint64_t xlen,
+                                                pangulu_uint64_t n_factors, void **workspace, void *caller_stream)
+    {
+        static_assert(sizeof(CondestResultD) == sizeof(pangulu_condest_result_t), "the kernel's result is the operator's");
+        if (step < PANGULU_CONDEST_FILL_INV_N || step > PANGULU_CONDEST_NORM1 || !workspace || n == 0)
+            return 0;
+        ensure_ready();
+        std::lock_guard<std::mutex> g(B.mutex);
+        HIP_CHECK(hipSetDevice(B.device));
+        if (!solve_pointer_on_device(d_x, sizeof(val_t) * (size_t)n) || (d_save && !solve_pointer_on_device(d_save, sizeof(val_t) * (size_t)n)))
+            return -1;
+        SolveWorkspace *ws = solve_workspace_of(workspace, (int)nb, (size_t)xlen, (size_t)n_factors);
+        if (!ws->d_condest_part)
+        {
+            solve_workspace_alloc(*ws, &ws->d_condest_part, (size_t)CONDEST_MAX_GROUPS);
+            solve_workspace_alloc(*ws, &ws->d_condest_res, (size_t)1);
+        }
+        HIP_CHECK(hipEventRecord(ws->after_caller, (hipStream_t)caller_stream));
+        HIP_CHECK(hipStreamWaitEvent(B.stream, ws->after_caller, 0));
+        const unsigned groups = condest_groups(n);
+        const size_t lds = 4 * sizeof(FsMax);
+        bool reduces = false;
+        switch (step)
+        {
+        case PANGULU_CONDEST_FILL_INV_N:
+        case PANGULU_CONDEST_SET_EJ:
+        case PANGULU_CONDEST_FILL_ALT:
+            hipLaunchKernelGGL(condest_fill_kernel, dim3(groups), dim3(FS_THREADS), 0, B.stream,
+                               step == PANGULU_CONDEST_FILL_INV_N ? CONDEST_FILL_INV_N : step == PANGULU_CONDEST_SET_EJ ? CONDEST_SET_EJ : CONDEST_FILL_ALT, d_x,
+                               (unsigned long long)n, (unsigned long long)j, groups);
+            break;
+        case PANGULU_CONDEST_NORM1_SIGN:
+        case PANGULU_CONDEST_NORM1:
+        {
+            const int with_sign = step == PANGULU_CONDEST_NORM1_SIGN;
+            hipLaunchKernelGGL(condest_norm1_kernel, dim3(groups), dim3(FS_THREADS), lds, B.stream, d_x, with_sign ? d_save : (val_t *)nullptr,
+                               (unsigned long long)n, with_sign, groups, ws->d_condest_part);
+            hipLaunchKernelGGL(condest_last_kernel, dim3(1), dim3(FS_THREADS), lds, B.stream, CONDEST_LAST_NORM1, ws->d_condest_part, groups, d_x,
+                               (unsigned long long)n, 0ull, (with_sign && d_save && j != 0) ? 1 : 0, ws->d_condest_res);
+            reduces = true;
+            break;
+        }
+        default: // PANGULU_CONDEST_ARGMAX
+            hipLaunchKernelGGL(condest_argmax_kernel, dim3(groups), dim3(FS_THREADS), lds, B.stream, d_x, (unsigned long long)n, groups, ws->d_condest_part);
+            hipLaunchKernelGGL(condest_last_kernel, dim3(1), dim3(FS_THREADS), lds, B.stream, CONDEST_LAST_ARGMAX, ws->d_condest_part, groups, d_x,
+                               (unsigned long long)n, (unsigned long long)j, 0, ws->d_condest_res);
+            reduces = true;
+            break;
+        }
+        HIP_CHECK(hipGetLastError());
+        if (reduces && out)
+            HIP_CHECK(hipMemcpyAsync(out, ws->d_condest_res, sizeof(CondestResultD), hipMemcpyDeviceToHost, B.stream));
+        HIP_CHECK(hipStreamSynchronize(B.stream));
+        return 1;
     }
 
     void pangulu_platform_0201001_block_spmv_add(pangulu_inblock_idx nb, pangulu_uint64_t nblk, pangulu_storage_slot_t *const *slots,

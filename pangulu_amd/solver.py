@@ -323,6 +323,51 @@ def factor_check_vectors(h, nvec=8, seed=20251003):
     return float(out.value)
 
 
+def factor_stats(h):
+    """pangulu_amd_factor_stats as a dict of the struct's fields plus "det": (mantissa, exponent) with det(A) = mantissa * 2**exponent
+    (a complex mantissa for complex value types); collective over the ranks."""
+    st = _lib.FactorStats()
+    rc = h.lib.pangulu_amd_factor_stats(h.ref, ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError("pangulu_amd_factor_stats: the handle has not been factorised")
+    out = st.as_dict()
+    cplx = np.issubdtype(np.dtype(h.dtype), np.complexfloating)
+    mant = complex(st.det_mantissa_re, st.det_mantissa_im) if cplx else float(st.det_mantissa_re)
+    out["det"] = (mant, int(st.det_exponent))
+    return out
+
+
+def slogdet(h):
+    """(sign, log|det(A)|) of the user's matrix from the factors, with numpy.linalg.slogdet's conventions: sign is +-1 (a complex
+    number of modulus 1 for complex value types), and (0, -inf) for a zero determinant."""
+    st = factor_stats(h)
+    mant, _ = st["det"]
+    if mant == 0:
+        return (0j if isinstance(mant, complex) else 0.0), -np.inf
+    sign = mant / abs(mant)
+    return sign, float(st["log_abs_det"])
+
+
+def rcond(h, norm="1", details=False):
+    """pangulu_amd_rcond: the estimated reciprocal condition number of the user's matrix in the 1-norm ("1", "O") or the infinity
+    norm ("I"); with details a dict of rcond, anorm, ainv_norm, solves and on_device.  Collective over the ranks."""
+    key = str(norm).upper()
+    if key in ("1", "O"):
+        code = _lib.NORM_ONE
+    elif key == "I":
+        code = _lib.NORM_INF
+    else:
+        raise ValueError("norm must be '1' or 'I', not %r" % (norm,))
+    rc_, an, ai = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    ns, dev = ctypes.c_int(), ctypes.c_int()
+    rc = h.lib.pangulu_amd_rcond(code, ctypes.byref(rc_), ctypes.byref(an), ctypes.byref(ai), ctypes.byref(ns), ctypes.byref(dev), h.ref)
+    if rc != 0:
+        raise RuntimeError("pangulu_amd_rcond failed (%d): %s" % (rc, "the handle has not been factorised" if rc == 1 else "unknown norm"))
+    if not details:
+        return float(rc_.value)
+    return {"rcond": float(rc_.value), "anorm": float(an.value), "ainv_norm": float(ai.value), "solves": int(ns.value), "on_device": int(dev.value)}
+
+
 MODEL_FIELDS = ("T_star_s", "sum_over_ranks_s", "link_term_s_max", "sent_bytes", "critical_path_s", "latency_chain_s", "rank_flop_share",
                 "rank_T_star_share", "hbm_bytes_fullest_rank", "hbm_records_owned", "hbm_records_received", "hbm_dense_mirrors")
 

@@ -1,6 +1,6 @@
 """One GPU, one handle: what a block of right-hand sides costs beside single pangulu_gstrs calls on the same factors.
 
-    python tools/bench_solve.py [--matrix elastic3d] [--size 48] [--nb 256] [--vtype r64] [--nrhs 1,4,16,64] [--repeats 5] [--trans N|T|H] [--device-rhs]
+    python tools/bench_solve.py [--matrix elastic3d] [--size 48] [--nb 256] [--vtype r64] [--nrhs 1,4,16,64] [--repeats 5] [--trans N|T|H] [--device-rhs] [--rcond]
 
 After pangulu_gstrf it times, in this process, the median of `repeats` single pangulu_gstrs calls and the median of `repeats`
 pangulu_gstrs_multi calls per nrhs, and prints one JSON line: the times, the time per column, the panels, the factor bytes a panel
@@ -10,7 +10,9 @@ their untransposed twins: a transposed sweep streams the same factor bytes, so t
 (matrices here are symmetric or nearly so: the residual is that of the transposed system all the same).  --device-rhs also times pangulu_amd_gstrs_device
 on a column-major device buffer beside pangulu_amd_gstrs_multi / _trans on a host buffer of the same handle, the raw C calls in place, per nrhs
 (and for --trans): both return synchronised, so a host perf_counter around the call is the time; the host-pointer call is the yardstick and
-its own spread (min .. max of the repeats) the margin.  (Run it through `tools/gpu_job.sh solve`, which puts it under a time limit.)"""
+its own spread (min .. max of the repeats) the margin.  --rcond times pangulu_amd_rcond (1-norm) and prints its number of solves and its
+milliseconds beside `solves` x the time of one single-column pangulu_amd_gstrs_device solve of the same run (the mean of the A and the A^H
+solve: the estimator alternates between them), so that what the vector kernels and the read-backs between the solves cost is visible.  (Run it through `tools/gpu_job.sh solve`, which puts it under a time limit.)"""
 import argparse
 import ctypes
 import json
@@ -36,8 +38,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--trans", default="N", choices=["N", "T", "H"])
     ap.add_argument("--device-rhs", action="store_true")
+    ap.add_argument("--rcond", action="store_true")
     a = ap.parse_args()
-    if a.device_rhs:
+    if a.device_rhs or a.rcond:
         # torch brings a HIP runtime of its own under the same soname as the one the library links: a process gets whichever is loaded
         # first, and torch finds no device on the other one.  So torch first -- as in bench.py and the tests -- and both calls on it.
         import torch
@@ -149,6 +152,27 @@ def main():
                                          "worst_residual": float("%.2e" % max(trans_residual(Xt[:, j], Bw[:, j]) for j in range(w)))}
         if a.device_rhs:
             out["multi"][-1]["device_rhs"] = [device_beside_host(Bw, t) for t in (["N"] if a.trans == "N" else ["N", a.trans])]
+    if a.rcond:
+        import torch
+
+        opt = _lib.GstrsOptions()
+        dcol = torch.from_numpy(np.ascontiguousarray(B[:, 0])).cuda()
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        one_column = {}
+        for name, code in (("N", 0), ("H", 2)):
+            rc = lib.pangulu_amd_gstrs_device(ctypes.c_void_p(dcol.data_ptr()), 1, n, code, stream, ctypes.byref(opt), h.ref)
+            if rc == 0:  # (4: no device-resident path for this handle; the estimator then runs on the host as well)
+                one_column[name] = spread_of(lambda: lib.pangulu_amd_gstrs_device(ctypes.c_void_p(dcol.data_ptr()), 1, n, code, stream, ctypes.byref(opt), h.ref))
+        d = pa.rcond(h, "1", details=True)
+        t = spread_of(lambda: pa.rcond(h, "1"))
+        out["rcond"] = dict(d, norm="1", call_ms=round(1e3 * t["median_s"], 3), call_min_ms=round(1e3 * t["min_s"], 3), call_max_ms=round(1e3 * t["max_s"], 3))
+        if len(one_column) == 2:
+            single = 0.5 * (one_column["N"]["median_s"] + one_column["H"]["median_s"])
+            out["rcond"].update({"device_rhs_single_column_ms": {k: round(1e3 * v["median_s"], 3) for k, v in one_column.items()},
+                                 "solves_x_single_column_ms": round(1e3 * d["solves"] * single, 3),
+                                 "call_vs_solves": round(t["median_s"] / (d["solves"] * single), 3)})
+        print("rcond_1 = %.6e: %d solves, %.3f ms (solves x one device-rhs single-column solve: %s ms)"
+              % (d["rcond"], d["solves"], out["rcond"]["call_ms"], out["rcond"].get("solves_x_single_column_ms", "n/a")), flush=True)
     pa.pangulu_finalize(h)
     print(json.dumps(out), flush=True)
 
