@@ -214,11 +214,47 @@ void solution_out_of_factor_space(const SolveMaps &M, u32 n, const val_t *b, val
         if (M.out_idx[i] != SOLVE_MAP_PAD)
             rhs[M.out_idx[i]] = scaled ? value_times(b[i], M.s_out[i]) : b[i];
 }
-void rhs_to_factor_space(Solver &S, const val_t *rhs, val_t *b) { rhs_into_factor_space(solve_maps(S, false), S.n, rhs, b); }
-void solution_from_factor_space(Solver &S, const val_t *b, val_t *rhs) { solution_out_of_factor_space(solve_maps(S, false), S.n, b, rhs); }
-void rhs_to_factor_space_trans(Solver &S, const val_t *rhs, val_t *b) { rhs_into_factor_space(solve_maps(S, true), S.n, rhs, b); }
-void solution_from_factor_space_trans(Solver &S, const val_t *b, val_t *rhs) { solution_out_of_factor_space(solve_maps(S, true), S.n, b, rhs); }
+
+void require_gstrs_options(const pangulu_gstrs_options *gstrs_options)
+{
+    if (gstrs_options != nullptr)
+        return;
+    if (world()->rank == 0)
+        printf("[PanguLU ERROR] Invalid input parameter. gstrs option struct pointer is NULL. Exit.\n");
+    exit(1);
+}
 } // namespace
+
+double pg::collective_column_solve(Solver &S, val_t *rhs, u32 nrhs, u64 ldb, int trans, bool single_vector)
+{
+    Comm *comm = world();
+    const bool transposed = trans != PANGULU_AMD_TRANS_NONE;
+    std::vector<val_t> b((size_t)S.n * nrhs);
+    if (comm->rank == 0)
+        for (u32 j = 0; j < nrhs; j++)
+            rhs_into_factor_space(solve_maps(S, transposed), S.n, rhs + (size_t)j * ldb, b.data() + (size_t)j * S.n);
+    comm->bcast(b.data(), sizeof(val_t) * b.size(), 0);
+    comm->barrier();
+    const double t0 = wall_seconds();
+    if (transposed)
+    {
+#ifdef PANGULU_COMPLEX
+        const bool conjugate = trans == PANGULU_AMD_TRANS_H;
+#else
+        const bool conjugate = false; // real values: A^H = A^T
+#endif
+        triangular_solve_multi_trans(S, b.data(), nrhs, conjugate);
+    }
+    else if (single_vector)
+        triangular_solve(S, b.data());
+    else
+        triangular_solve_multi(S, b.data(), nrhs);
+    const double sweep_seconds = wall_seconds() - t0;
+    if (comm->rank == 0)
+        for (u32 j = 0; j < nrhs; j++)
+            solution_out_of_factor_space(solve_maps(S, transposed), S.n, b.data() + (size_t)j * S.n, rhs + (size_t)j * ldb);
+    return sweep_seconds;
+}
 
 extern "C"
 {
@@ -765,78 +801,22 @@ extern "C"
 
     void pangulu_gstrs(sparse_value_t *rhs, pangulu_gstrs_options *gstrs_options, void **pangulu_handle)
     {
-        if (gstrs_options == nullptr)
-        {
-            if (world()->rank == 0)
-                printf("[PanguLU ERROR] Invalid input parameter. gstrs option struct pointer is NULL. Exit.\n");
-            exit(1);
-        }
+        require_gstrs_options(gstrs_options);
         Solver *S = (Solver *)*pangulu_handle;
         NearDevice near(active_platform());
-        Comm *comm = world();
-        std::vector<val_t> b(S->n);
-        if (comm->rank == 0)
-            rhs_to_factor_space(*S, rhs, b.data());
-        comm->bcast(b.data(), sizeof(val_t) * S->n, 0);
-        comm->barrier();
-        double t0 = wall_seconds();
-        triangular_solve(*S, b.data());
-        S->info.time_solve = wall_seconds() - t0;
-        if (comm->rank == 0)
-            solution_from_factor_space(*S, b.data(), rhs);
+        S->info.time_solve = collective_column_solve(*S, rhs, 1, S->n_user, PANGULU_AMD_TRANS_NONE, true);
     }
 
-    int pangulu_amd_gstrs_multi(sparse_value_t *rhs, sparse_index_t nrhs, sparse_pointer_t ldb, pangulu_gstrs_options *gstrs_options, void **pangulu_handle)
-    {
-        if (gstrs_options == nullptr)
-        {
-            if (world()->rank == 0)
-                printf("[PanguLU ERROR] Invalid input parameter. gstrs option struct pointer is NULL. Exit.\n");
-            exit(1);
-        }
-        Solver *S = (Solver *)*pangulu_handle;
-        if (!S->factored)
-            return 1;
-        const double t0 = wall_seconds();
-        NearDevice near(active_platform());
-        Comm *comm = world();
-        // rank 0's arguments decide for everybody
-        unsigned long long head[2] = {0, (unsigned long long)nrhs};
-        if (comm->rank == 0 && nrhs != 0 && (rhs == nullptr || ldb < (sparse_pointer_t)S->n_user))
-            head[0] = 2;
-        comm->bcast(head, sizeof(head), 0);
-        if (head[0] != 0)
-            return (int)head[0];
-        nrhs = (sparse_index_t)head[1];
-        if (nrhs == 0)
-            return 0;
-        std::vector<val_t> b((size_t)S->n * nrhs);
-        if (comm->rank == 0)
-            for (sparse_index_t j = 0; j < nrhs; j++)
-                rhs_to_factor_space(*S, rhs + (size_t)j * ldb, b.data() + (size_t)j * S->n);
-        comm->bcast(b.data(), sizeof(val_t) * b.size(), 0);
-        comm->barrier();
-        triangular_solve_multi(*S, b.data(), (u32)nrhs);
-        if (comm->rank == 0)
-            for (sparse_index_t j = 0; j < nrhs; j++)
-                solution_from_factor_space(*S, b.data() + (size_t)j * S->n, rhs + (size_t)j * ldb);
-        S->info.time_solve = wall_seconds() - t0;
-        return 0;
-    }
-
+    // A^T X = B / A^H X = B, and with trans = PANGULU_AMD_TRANS_NONE what pangulu_amd_gstrs_multi does
     int pangulu_amd_gstrs_trans(sparse_value_t *rhs, sparse_index_t nrhs, sparse_pointer_t ldb, int trans, pangulu_gstrs_options *gstrs_options,
                                 void **pangulu_handle)
     {
-        if (gstrs_options == nullptr)
-        {
-            if (world()->rank == 0)
-                printf("[PanguLU ERROR] Invalid input parameter. gstrs option struct pointer is NULL. Exit.\n");
-            exit(1);
-        }
+        require_gstrs_options(gstrs_options);
         Solver *S = (Solver *)*pangulu_handle;
         if (!S->factored)
             return 1;
         const double t0 = wall_seconds();
+        NearDevice near(active_platform());
         Comm *comm = world();
         // rank 0's arguments decide for everybody
         unsigned long long head[3] = {0, (unsigned long long)nrhs, (unsigned long long)(unsigned)trans};
@@ -850,41 +830,22 @@ extern "C"
         comm->bcast(head, sizeof(head), 0);
         if (head[0] != 0)
             return (int)head[0];
-        trans = (int)head[2];
-        if (trans == PANGULU_AMD_TRANS_NONE)
-            return pangulu_amd_gstrs_multi(rhs, nrhs, ldb, gstrs_options, pangulu_handle);
-        NearDevice near(active_platform());
-        nrhs = (sparse_index_t)head[1];
-        if (nrhs == 0)
+        if (head[1] == 0)
             return 0;
-        std::vector<val_t> b((size_t)S->n * nrhs);
-        if (comm->rank == 0)
-            for (sparse_index_t j = 0; j < nrhs; j++)
-                rhs_to_factor_space_trans(*S, rhs + (size_t)j * ldb, b.data() + (size_t)j * S->n);
-        comm->bcast(b.data(), sizeof(val_t) * b.size(), 0);
-        comm->barrier();
-#ifdef PANGULU_COMPLEX
-        const bool conjugate = trans == PANGULU_AMD_TRANS_H;
-#else
-        const bool conjugate = false; // real values: A^H = A^T
-#endif
-        triangular_solve_multi_trans(*S, b.data(), (u32)nrhs, conjugate);
-        if (comm->rank == 0)
-            for (sparse_index_t j = 0; j < nrhs; j++)
-                solution_from_factor_space_trans(*S, b.data() + (size_t)j * S->n, rhs + (size_t)j * ldb);
+        collective_column_solve(*S, rhs, (u32)head[1], (u64)ldb, (int)head[2]);
         S->info.time_solve = wall_seconds() - t0;
         return 0;
+    }
+
+    int pangulu_amd_gstrs_multi(sparse_value_t *rhs, sparse_index_t nrhs, sparse_pointer_t ldb, pangulu_gstrs_options *gstrs_options, void **pangulu_handle)
+    {
+        return pangulu_amd_gstrs_trans(rhs, nrhs, ldb, PANGULU_AMD_TRANS_NONE, gstrs_options, pangulu_handle);
     }
 
     int pangulu_amd_gstrs_device(sparse_value_t *d_rhs, sparse_index_t nrhs, sparse_pointer_t ldb, int trans, void *stream,
                                  pangulu_gstrs_options *gstrs_options, void **pangulu_handle)
     {
-        if (gstrs_options == nullptr)
-        {
-            if (world()->rank == 0)
-                printf("[PanguLU ERROR] Invalid input parameter. gstrs option struct pointer is NULL. Exit.\n");
-            exit(1);
-        }
+        require_gstrs_options(gstrs_options);
         Solver *S = (Solver *)*pangulu_handle;
         if (!S->factored)
             return 1;

@@ -8,8 +8,8 @@
 //                          then over the ranks in rank order on rank 0: the same call gives the same bits;
 //   reciprocal_condition   Higham's 1-norm estimator as LAPACK's xLACN2 states it, written ONCE over CondestOps: on a device vector
 //                          (Platform::condest_vector between triangular_solve_device calls; a few scalars come back per step) where
-//                          the device-resident solve exists for A and A^H, on a host vector through triangular_solve_multi /
-//                          triangular_solve_multi_trans everywhere else (rank 0 drives; one word per step tells the other ranks which
+//                          the device-resident solve exists for A and A^H, on a host vector through collective_column_solve
+//                          (pg_api.cpp) everywhere else (rank 0 drives; one word per step tells the other ranks which
 //                          solve comes next, or to leave).
 #include <algorithm>
 #include <cmath>
@@ -440,45 +440,11 @@ double estimate_inverse_norm1(CondestOps &ops, u64 n, int &solves, bool &saw_nan
     return est;
 }
 
-val_t scaled_value(val_t v, double s)
-{
-#ifdef PANGULU_COMPLEX
-    return val_t{(calculate_real_type)(v.re * s), (calculate_real_type)(v.im * s)};
-#else
-    return (val_t)(v * s);
-#endif
-}
-
 // One collective solve of the host path with the user's vector on rank 0: what pangulu_amd_gstrs_multi / _trans do with one column.
-// `x` is ignored on the other ranks.
+// `x` is ignored on the other ranks.  (real values: A^H = A^T)
 void collective_host_solve(Solver &S, val_t *x, bool adjoint)
 {
-    Comm *comm = world();
-    std::vector<val_t> b(S.n);
-    if (comm->rank == 0)
-    {
-        const SolveMaps &M = solve_maps(S, adjoint);
-        for (u32 i = 0; i < S.n; i++)
-        {
-            if (M.in_idx[i] == SOLVE_MAP_PAD)
-                memset(&b[i], 0, sizeof(val_t));
-            else
-                b[i] = M.s_in.empty() ? x[M.in_idx[i]] : scaled_value(x[M.in_idx[i]], M.s_in[i]);
-        }
-    }
-    comm->bcast(b.data(), sizeof(val_t) * S.n, 0);
-    comm->barrier();
-    if (adjoint)
-        triangular_solve_multi_trans(S, b.data(), 1, kComplex);
-    else
-        triangular_solve_multi(S, b.data(), 1);
-    if (comm->rank == 0)
-    {
-        const SolveMaps &M = solve_maps(S, adjoint);
-        for (u32 i = 0; i < S.n; i++)
-            if (M.out_idx[i] != SOLVE_MAP_PAD)
-                x[M.out_idx[i]] = M.s_out.empty() ? b[i] : scaled_value(b[i], M.s_out[i]);
-    }
+    collective_column_solve(S, x, 1, S.n_user, adjoint ? PANGULU_AMD_TRANS_H : PANGULU_AMD_TRANS_NONE);
 }
 
 constexpr u64 STEP_LEAVE = 0, STEP_SOLVE = 1, STEP_SOLVE_ADJOINT = 2;

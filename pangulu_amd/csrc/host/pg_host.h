@@ -387,13 +387,11 @@ struct Solver
     u64 pending_total = 0;
     bool factored = false, host_values_current = true;
     bool schedule_recorded = false;        // the back-end holds the launch list of this handle's factorisation (one rank)
-    // device solve (pangulu_gstrs and pangulu_amd_gstrs_multi on one rank): both sweeps' plans, built on first use (new values on the
-    // same pattern keep them: the records stay where they are); and what the last pangulu_amd_gstrs_multi did (pangulu_amd_last_solve_path)
-    SolveSweepPlan solve_plan[2];
-    bool solve_plan_ready = false;
-    // the transposed solve's plans (pangulu_amd_gstrs_trans): [0] forward with U^T, [1] backward with L^T, from the block-CSC side
-    SolveSweepPlan solve_plan_trans[2];
-    bool solve_plan_trans_ready = false;
+    // device solve (one rank): the sweeps' plans by direction and sweep, [0] = {L, U} for A x = b, [1] = {U^T forward, L^T backward}
+    // for the transposed solves, each direction built on first use (new values on the same pattern keep them: the records stay where
+    // they are); and what the last pangulu_amd_gstrs_multi did (pangulu_amd_last_solve_path)
+    SolveSweepPlan solve_plan[2][2];
+    bool solve_plan_ready[2] = {false, false};
     int last_solve_device_columns = 0, last_solve_panel_width = 0, last_solve_panels = 0;
     SolveMaps solve_maps[2];               // [0] untransposed, [1] transposed: built on first use, fixed for the handle's life
     // pangulu_amd_gstrs_device: what the back-end keeps on the device for this handle between calls (descriptors of the sweeps, panel
@@ -486,6 +484,11 @@ void triangular_solve_multi(Solver &S, val_t *B, u32 nrhs); // the same for n x 
 // through Platform::block_trsm_multi_trans where the device solve runs and offers it, the host sweep over block columns elsewhere
 void triangular_solve_multi_trans(Solver &S, val_t *B, u32 nrhs, bool conjugate);
 const SolveMaps &solve_maps(Solver &S, bool transposed);  // pg_api.cpp: the handle's maps for a direction, built on first use (rank 0)
+// pg_api.cpp, collective: rank 0's nrhs columns (column j at rhs + j ldb; `rhs` is ignored on the other ranks) into factor space
+// through solve_maps(), broadcast, the sweeps of `trans` (PANGULU_AMD_TRANS_*) on every rank, and the solutions back into rank 0's
+// columns.  PANGULU_AMD_TRANS_NONE runs triangular_solve_multi, or with `single_vector` (nrhs = 1) triangular_solve as pangulu_gstrs
+// does; _T / _H run triangular_solve_multi_trans.  Returns the seconds the sweeps alone took.
+double collective_column_solve(Solver &S, val_t *rhs, u32 nrhs, u64 ldb, int trans, bool single_vector = false);
 // The same solves for an ldb x nrhs column-major matrix in DEVICE memory, in and out of factor space on the device through solve_maps(),
 // ordered behind `stream` (one rank).  0: done; 2: the back-end refused the pointer; 4: no device-resident path for this handle (nothing touched)
 // reproducible: single-vector panels and no sums by atomics -- the same bits from call to call (pangulu_amd_rcond); 4 where the back-end lacks it

@@ -116,75 +116,47 @@ void block_lower_trans_solve(u32 nb, const slot_t *l, val_t *x, bool conj)
 
 } // namespace
 
-// The level structure of one sweep of the device solve: a pure function of the block pattern (and of the slots the records sit in).
-static void build_sweep_plan(const Solver &S, bool lower, SolveSweepPlan &plan)
+// One of the four sweeps of a solve -- L then U for A x = b, U^T then L^T for A^T x = b / A^H x = b -- as what it reads of the block
+// pattern.  Segment i of the vector receives the products of the blocks at the pattern positions begin[i] .. end[i]; position r is
+// block (i, neighbour[r]) of the block-CSR side (L, U) and reads segment neighbour[r], block (neighbour[r], i) of the block-CSC side
+// (U^T, L^T: block row i of U^T is block column i of U, so segment i reads the segments k < i of the blocks A(k, i), and with L^T
+// the segments k > i).  Then the diagonal owner solves with diag[i].
+struct SweepShape
+{
+    const u64 *begin, *end;   // per segment: pointers into BlockPattern (`end` possibly + 1)
+    const u32 *neighbour;     // colidx or rowidx
+    const u64 *to_block;      // position -> index of slot_of: csr_to_csc on the block-CSR side, nullptr (the position itself) on the block-CSC side
+    slot_t *const *diag;      // diag_lower or diag_upper
+    bool ascending;           // segments 0 .. nbk-1, or nbk-1 .. 0
+    u64 block_of(u64 r) const { return to_block ? to_block[r] : r; }
+    int owner_of(const Solver &S, u32 i, u64 r) const { return to_block ? S.owner(i, neighbour[r]) : S.owner(neighbour[r], i); }
+    u32 segment_at(u32 step, u32 nbk) const { return ascending ? step : nbk - 1 - step; }
+};
+
+static SweepShape sweep_shape(const Solver &S, bool transposed, int sweep)
 {
     const BlockPattern &P = S.pat;
-    const u32 nbk = S.nbk;
-    // level of a block row = 1 + the highest level among the rows its off-diagonal blocks (on the sweep's side) read
-    std::vector<u32> level(nbk, 0);
-    u32 nlevel = 0;
-    for (u32 step = 0; step < nbk; step++)
-    {
-        const u32 brow = lower ? step : nbk - 1 - step;
-        const u64 rb = lower ? P.rowptr[brow] : P.first_after_diag_csr[brow];
-        const u64 re = lower ? P.first_after_diag_csr[brow] : P.rowptr[brow + 1];
-        u32 lv = 0;
-        for (u64 r = rb; r < re; r++)
-            lv = std::max(lv, level[P.colidx[r]] + 1);
-        level[brow] = lv;
-        nlevel = std::max(nlevel, lv + 1);
-    }
-    plan.nlevel = nlevel;
-    plan.level_ptr.assign((size_t)nlevel + 1, 0);
-    for (u32 k = 0; k < nbk; k++)
-        plan.level_ptr[level[k] + 1]++;
-    for (u32 l = 0; l < nlevel; l++)
-        plan.level_ptr[l + 1] += plan.level_ptr[l];
-    plan.rows.assign(nbk, pangulu_hip_solve_row_t());
-    plan.blk_slots.clear();
-    plan.blk_bcol.clear();
-    std::vector<pangulu_uint64_t> cur(plan.level_ptr.begin(), plan.level_ptr.end() - 1);
-    for (u32 brow = 0; brow < nbk; brow++)
-    {
-        pangulu_hip_solve_row_t R;
-        R.brow = brow;
-        R.first = plan.blk_slots.size();
-        R.diag = lower ? S.diag_lower[brow] : S.diag_upper[brow];
-        const u64 rb = lower ? P.rowptr[brow] : P.first_after_diag_csr[brow];
-        const u64 re = lower ? P.first_after_diag_csr[brow] : P.rowptr[brow + 1];
-        for (u64 r = rb; r < re; r++)
-        {
-            plan.blk_slots.push_back(S.slot_of[P.csr_to_csc[r]]);
-            plan.blk_bcol.push_back(P.colidx[r]);
-        }
-        R.nblk = (pangulu_exblock_idx)(plan.blk_slots.size() - R.first);
-        plan.rows[cur[level[brow]]++] = R;
-    }
-    if (plan.blk_slots.empty())
-    {
-        plan.blk_slots.push_back(nullptr);
-        plan.blk_bcol.push_back(0);
-    }
+    if (!transposed)
+        return sweep == 0 ? SweepShape{P.rowptr.data(), P.first_after_diag_csr.data(), P.colidx.data(), P.csr_to_csc.data(), S.diag_lower.data(), true}
+                          : SweepShape{P.first_after_diag_csr.data(), P.rowptr.data() + 1, P.colidx.data(), P.csr_to_csc.data(), S.diag_upper.data(), false};
+    return sweep == 0 ? SweepShape{P.colptr.data(), P.first_after_diag.data(), P.rowidx.data(), nullptr, S.diag_upper.data(), true}
+                      : SweepShape{P.first_after_diag.data(), P.colptr.data() + 1, P.rowidx.data(), nullptr, S.diag_lower.data(), false};
 }
 
-// The same for the transposed solve, from the block-CSC side of the pattern: block row i of U^T is block column i of U, so in the
-// forward sweep (U^T) segment i reads the segments k < i of the blocks A(k, i), and in the backward sweep (L^T) the segments k > i.
-// `brow` of a row is the destination segment i, blk_bcol the source segment k, `diag` the upper half (forward) / the lower half.
-static void build_trans_sweep_plan(const Solver &S, bool forward, SolveSweepPlan &plan)
+// The level structure of one sweep of the device solve: a pure function of the block pattern (and of the slots the records sit in).
+// `brow` of a row is the destination segment i, blk_bcol the source segment, `diag` the sweep's diagonal half.
+static void build_sweep_plan(const Solver &S, const SweepShape &sweep, SolveSweepPlan &plan)
 {
-    const BlockPattern &P = S.pat;
     const u32 nbk = S.nbk;
-    auto begin_of = [&](u32 i) { return forward ? P.colptr[i] : P.first_after_diag[i]; };
-    auto end_of = [&](u32 i) { return forward ? P.first_after_diag[i] : P.colptr[i + 1]; };
+    // level of a segment = 1 + the highest level among the segments its off-diagonal blocks (on the sweep's side) read
     std::vector<u32> level(nbk, 0);
     u32 nlevel = 0;
     for (u32 step = 0; step < nbk; step++)
     {
-        const u32 i = forward ? step : nbk - 1 - step;
+        const u32 i = sweep.segment_at(step, nbk);
         u32 lv = 0;
-        for (u64 b = begin_of(i); b < end_of(i); b++)
-            lv = std::max(lv, level[P.rowidx[b]] + 1);
+        for (u64 r = sweep.begin[i]; r < sweep.end[i]; r++)
+            lv = std::max(lv, level[sweep.neighbour[r]] + 1);
         level[i] = lv;
         nlevel = std::max(nlevel, lv + 1);
     }
@@ -203,11 +175,11 @@ static void build_trans_sweep_plan(const Solver &S, bool forward, SolveSweepPlan
         pangulu_hip_solve_row_t R;
         R.brow = i;
         R.first = plan.blk_slots.size();
-        R.diag = forward ? S.diag_upper[i] : S.diag_lower[i];
-        for (u64 b = begin_of(i); b < end_of(i); b++)
+        R.diag = sweep.diag[i];
+        for (u64 r = sweep.begin[i]; r < sweep.end[i]; r++)
         {
-            plan.blk_slots.push_back(S.slot_of[b]);
-            plan.blk_bcol.push_back(P.rowidx[b]);
+            plan.blk_slots.push_back(S.slot_of[sweep.block_of(r)]);
+            plan.blk_bcol.push_back(sweep.neighbour[r]);
         }
         R.nblk = (pangulu_exblock_idx)(plan.blk_slots.size() - R.first);
         plan.rows[cur[level[i]]++] = R;
@@ -229,21 +201,16 @@ static bool device_solve_enabled(const Solver &S, const Platform &plat)
 // the two sweeps of a direction as the platform operators take them, from the handle's plans (built here on first use)
 static void solve_sweeps_of(Solver &S, int trans, pangulu_hip_solve_sweep_t sw[2])
 {
-    if (trans == PANGULU_AMD_TRANS_NONE && !S.solve_plan_ready)
+    const int d = trans == PANGULU_AMD_TRANS_NONE ? 0 : 1;
+    if (!S.solve_plan_ready[d])
     {
-        build_sweep_plan(S, true, S.solve_plan[0]);
-        build_sweep_plan(S, false, S.solve_plan[1]);
-        S.solve_plan_ready = true;
-    }
-    if (trans != PANGULU_AMD_TRANS_NONE && !S.solve_plan_trans_ready)
-    {
-        build_trans_sweep_plan(S, true, S.solve_plan_trans[0]);
-        build_trans_sweep_plan(S, false, S.solve_plan_trans[1]);
-        S.solve_plan_trans_ready = true;
+        for (int s = 0; s < 2; s++)
+            build_sweep_plan(S, sweep_shape(S, d == 1, s), S.solve_plan[d][s]);
+        S.solve_plan_ready[d] = true;
     }
     for (int s = 0; s < 2; s++)
     {
-        const SolveSweepPlan &pl = trans == PANGULU_AMD_TRANS_NONE ? S.solve_plan[s] : S.solve_plan_trans[s];
+        const SolveSweepPlan &pl = S.solve_plan[d][s];
         sw[s].nlevel = pl.nlevel;
         sw[s].level_ptr = pl.level_ptr.data();
         sw[s].rows = pl.rows.data();
@@ -277,6 +244,81 @@ static void device_solve_panels(Solver &S, Platform &plat, val_t *X, size_t npan
             plat.block_trsv((pangulu_inblock_idx)S.nb, s, sw[s].nlevel, sw[s].level_ptr, sw[s].rows, sw[s].blk_slots, sw[s].blk_bcol, X + p * xlen, xlen);
 }
 
+// One sweep of the host solve across the ranks, segment by segment in the sweep's direction: every rank that owns blocks of the
+// segment on the sweep's side (with the subtree mapping these are not confined to the diagonal owner's process row / column) adds the
+// products of its own blocks with `spmv`, the diagonal owner sums the partial vectors in rank order, solves with its diagonal half
+// (`diag_solve`) and broadcasts the finished segment.  A partial vector of segment i travels under tag_base + (i & 0xfffff):
+// 0x100000 for the untransposed sweeps, 0x200000 for the transposed ones.
+template <class Spmv, class DiagSolve>
+static void host_sweep(Solver &S, const SweepShape &sweep, int tag_base, Spmv spmv, DiagSolve diag_solve, std::vector<val_t> &x)
+{
+    Comm *comm = world();
+    const u32 nb = S.nb, nbk = S.nbk;
+    const int me = S.rank;
+    std::vector<char> contributes((size_t)S.nproc, 0);
+    std::vector<val_t> acc(nb), tmp(nb);
+    for (u32 step = 0; step < nbk; step++)
+    {
+        const u32 i = sweep.segment_at(step, nbk);
+        val_t *seg = x.data() + (size_t)i * nb;
+        const int diag_rank = S.owner(i, i);
+        const int tag = tag_base + (int)(i & 0xfffff);
+        std::fill(contributes.begin(), contributes.end(), 0);
+        for (u64 r = sweep.begin[i]; r < sweep.end[i]; r++)
+            contributes[(size_t)sweep.owner_of(S, i, r)] = 1;
+        if (contributes[(size_t)me] || me == diag_rank)
+        {
+            std::fill(acc.begin(), acc.end(), vmake(0));
+            for (u64 r = sweep.begin[i]; r < sweep.end[i]; r++)
+                if (sweep.owner_of(S, i, r) == me)
+                    spmv(S.slot_of[sweep.block_of(r)], x.data() + (size_t)sweep.neighbour[r] * nb, acc.data());
+            if (me == diag_rank)
+            {
+                for (int r = 0; r < S.nproc; r++)
+                {
+                    if (r == me || !contributes[(size_t)r])
+                        continue;
+                    comm->recv_bytes(r, tag, tmp.data(), sizeof(val_t) * nb);
+                    for (u32 k = 0; k < nb; k++)
+                        acc[k] = vadd(acc[k], tmp[k]);
+                }
+                for (u32 k = 0; k < nb; k++)
+                    seg[k] = vadd(seg[k], acc[k]);
+                diag_solve(sweep.diag[i], seg);
+            }
+            else
+            {
+                comm->send_bytes(diag_rank, tag, acc.data(), sizeof(val_t) * nb);
+            }
+        }
+        comm->bcast(seg, sizeof(val_t) * nb, diag_rank);
+    }
+    comm->barrier();
+}
+
+// Both sweeps on the host copies of the factors for one vector, everywhere the device solve does not run (collective): L then U
+// over block rows, or (transposed) U^T then L^T over block columns with op() = conjugation for A^H.
+static void host_solve(Solver &S, val_t *rhs, bool transposed, bool conj)
+{
+    download_factors(S);
+    const u32 nb = S.nb;
+    std::vector<val_t> x((size_t)S.nbk * nb, vmake(0));
+    std::copy(rhs, rhs + S.n, x.begin());
+    for (int s = 0; s < 2; s++)
+    {
+        const SweepShape sweep = sweep_shape(S, transposed, s);
+        if (!transposed)
+            host_sweep(
+                S, sweep, 0x100000, [&](const slot_t *a, const val_t *xk, val_t *y) { block_spmv(nb, a, xk, y); },
+                [&](const slot_t *d, val_t *seg) { s == 0 ? block_lower_solve(nb, d, seg) : block_upper_solve(nb, d, seg); }, x);
+        else
+            host_sweep(
+                S, sweep, 0x200000, [&](const slot_t *a, const val_t *xk, val_t *y) { block_spmv_trans(nb, a, xk, y, conj); },
+                [&](const slot_t *d, val_t *seg) { s == 0 ? block_upper_trans_solve(nb, d, seg, conj) : block_lower_trans_solve(nb, d, seg, conj); }, x);
+    }
+    std::copy(x.begin(), x.begin() + S.n, rhs);
+}
+
 void triangular_solve(Solver &S, val_t *rhs)
 {
     Platform &plat = active_platform();
@@ -290,70 +332,7 @@ void triangular_solve(Solver &S, val_t *rhs)
         std::copy(x.begin(), x.begin() + S.n, rhs);
         return;
     }
-    download_factors(S);
-    Comm *comm = world();
-    const BlockPattern &P = S.pat;
-    u32 nb = S.nb, nbk = S.nbk;
-    int me = S.rank;
-    std::vector<char> contributes((size_t)S.nproc, 0);
-    std::vector<val_t> x((size_t)nbk * nb, vmake(0)), acc(nb), tmp(nb);
-    std::copy(rhs, rhs + S.n, x.begin());
-    const int TAG_PART = 0x100000;
-
-    for (int pass = 0; pass < 2; pass++)
-    {
-        bool lower = pass == 0;
-        for (u32 step = 0; step < nbk; step++)
-        {
-            u32 brow = lower ? step : nbk - 1 - step;
-            val_t *seg = x.data() + (size_t)brow * nb;
-            int diag_rank = S.owner(brow, brow);
-            // the ranks that hold blocks of block row brow on the relevant side of the diagonal (with the subtree
-            // mapping these are not confined to the diagonal owner's process row): each adds the products of its
-            // own blocks, the diagonal owner sums the partial vectors
-            u64 rb = lower ? P.rowptr[brow] : P.first_after_diag_csr[brow];
-            u64 re = lower ? P.first_after_diag_csr[brow] : P.rowptr[brow + 1];
-            std::fill(contributes.begin(), contributes.end(), 0);
-            for (u64 r = rb; r < re; r++)
-                contributes[(size_t)S.owner(brow, P.colidx[r])] = 1;
-            if (contributes[(size_t)me] || me == diag_rank)
-            {
-                std::fill(acc.begin(), acc.end(), vmake(0));
-                for (u64 r = rb; r < re; r++)
-                {
-                    u32 bcol = P.colidx[r];
-                    if (S.owner(brow, bcol) != me)
-                        continue;
-                    slot_t *blk = S.slot_of[P.csr_to_csc[r]];
-                    block_spmv(nb, blk, x.data() + (size_t)bcol * nb, acc.data());
-                }
-                if (me == diag_rank)
-                {
-                    for (int r = 0; r < S.nproc; r++)
-                    {
-                        if (r == me || !contributes[(size_t)r])
-                            continue;
-                        comm->recv_bytes(r, TAG_PART + (int)(brow & 0xfffff), tmp.data(), sizeof(val_t) * nb);
-                        for (u32 i = 0; i < nb; i++)
-                            acc[i] = vadd(acc[i], tmp[i]);
-                    }
-                    for (u32 i = 0; i < nb; i++)
-                        seg[i] = vadd(seg[i], acc[i]);
-                    if (lower)
-                        block_lower_solve(nb, S.diag_lower[brow], seg);
-                    else
-                        block_upper_solve(nb, S.diag_upper[brow], seg);
-                }
-                else
-                {
-                    comm->send_bytes(diag_rank, TAG_PART + (int)(brow & 0xfffff), acc.data(), sizeof(val_t) * nb);
-                }
-            }
-            comm->bcast(seg, sizeof(val_t) * nb, diag_rank);
-        }
-        comm->barrier();
-    }
-    std::copy(x.begin(), x.begin() + S.n, rhs);
+    host_solve(S, rhs, false, false);
 }
 
 // panels for nrhs columns: the widest width while that many columns are left, then the smallest power of two that holds the rest (zero columns pad it)
@@ -433,74 +412,6 @@ void triangular_solve_multi(Solver &S, val_t *Bm, u32 nrhs)
     device_solve_columns(S, plat, Bm, nrhs, wmax, PANGULU_AMD_TRANS_NONE);
 }
 
-// The host sweep of the transposed solve for one vector, everywhere the device solve does not run: the loop of triangular_solve()
-// over block COLUMNS.  Forward with U^T: segment i receives -op(U(k, i))^T x_k from the blocks k < i of block column i, whose owners
-// contribute; the diagonal owner sums the partial vectors (tags of their own), solves with the transpose of its upper half and
-// broadcasts the segment.  Backward with L^T: the blocks k > i and the transpose of the unit lower half.
-static void triangular_solve_trans(Solver &S, val_t *rhs, bool conj)
-{
-    download_factors(S);
-    Comm *comm = world();
-    const BlockPattern &P = S.pat;
-    u32 nb = S.nb, nbk = S.nbk;
-    int me = S.rank;
-    std::vector<char> contributes((size_t)S.nproc, 0);
-    std::vector<val_t> x((size_t)nbk * nb, vmake(0)), acc(nb), tmp(nb);
-    std::copy(rhs, rhs + S.n, x.begin());
-    const int TAG_PART_TRANS = 0x200000;
-
-    for (int pass = 0; pass < 2; pass++)
-    {
-        bool forward = pass == 0;
-        for (u32 step = 0; step < nbk; step++)
-        {
-            u32 bcol = forward ? step : nbk - 1 - step;
-            val_t *seg = x.data() + (size_t)bcol * nb;
-            int diag_rank = S.owner(bcol, bcol);
-            u64 cb = forward ? P.colptr[bcol] : P.first_after_diag[bcol];
-            u64 ce = forward ? P.first_after_diag[bcol] : P.colptr[bcol + 1];
-            std::fill(contributes.begin(), contributes.end(), 0);
-            for (u64 b = cb; b < ce; b++)
-                contributes[(size_t)S.owner(P.rowidx[b], bcol)] = 1;
-            if (contributes[(size_t)me] || me == diag_rank)
-            {
-                std::fill(acc.begin(), acc.end(), vmake(0));
-                for (u64 b = cb; b < ce; b++)
-                {
-                    u32 brow = P.rowidx[b];
-                    if (S.owner(brow, bcol) != me)
-                        continue;
-                    block_spmv_trans(nb, S.slot_of[b], x.data() + (size_t)brow * nb, acc.data(), conj);
-                }
-                if (me == diag_rank)
-                {
-                    for (int r = 0; r < S.nproc; r++)
-                    {
-                        if (r == me || !contributes[(size_t)r])
-                            continue;
-                        comm->recv_bytes(r, TAG_PART_TRANS + (int)(bcol & 0xfffff), tmp.data(), sizeof(val_t) * nb);
-                        for (u32 i = 0; i < nb; i++)
-                            acc[i] = vadd(acc[i], tmp[i]);
-                    }
-                    for (u32 i = 0; i < nb; i++)
-                        seg[i] = vadd(seg[i], acc[i]);
-                    if (forward)
-                        block_upper_trans_solve(nb, S.diag_upper[bcol], seg, conj);
-                    else
-                        block_lower_trans_solve(nb, S.diag_lower[bcol], seg, conj);
-                }
-                else
-                {
-                    comm->send_bytes(diag_rank, TAG_PART_TRANS + (int)(bcol & 0xfffff), acc.data(), sizeof(val_t) * nb);
-                }
-            }
-            comm->bcast(seg, sizeof(val_t) * nb, diag_rank);
-        }
-        comm->barrier();
-    }
-    std::copy(x.begin(), x.begin() + S.n, rhs);
-}
-
 void triangular_solve_multi_trans(Solver &S, val_t *Bm, u32 nrhs, bool conjugate)
 {
     Platform &plat = active_platform();
@@ -513,7 +424,7 @@ void triangular_solve_multi_trans(Solver &S, val_t *Bm, u32 nrhs, bool conjugate
     if (wmax < 1)
     {
         for (u32 j = 0; j < nrhs; j++)
-            triangular_solve_trans(S, Bm + (size_t)j * S.n, conjugate);
+            host_solve(S, Bm + (size_t)j * S.n, true, conjugate);
         return;
     }
     device_solve_columns(S, plat, Bm, nrhs, wmax, conjugate ? PANGULU_AMD_TRANS_H : PANGULU_AMD_TRANS_T);

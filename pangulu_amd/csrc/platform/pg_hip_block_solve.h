@@ -1,5 +1,6 @@
-// pg_hip_block_solve.h -- the descriptors of the level-scheduled block triangular solve, its column-by-column kernels and the
-// kernel of the device-side factor check.  Included inside the anonymous namespace of pg_hip_platform.hip.
+// pg_hip_block_solve.h -- the column-by-column kernels of the level-scheduled block triangular solve and the kernel of the
+// device-side factor check.  Included inside the anonymous namespace of pg_hip_platform.hip, after pg_hip_block_solve_multi.h
+// (the descriptors SolveBlkD / SolveRowD).
 #pragma once
 
 // -----------------------------------------------------------------------------------------------------------------
@@ -16,23 +17,6 @@
 // from HBM and takes single vectors only: PANGULU_HIP_SOLVE_CHUNKED=0 selects it, and it is what is left when nb is so large
 // that not even one chunk column of a diagonal half fits in LDS beside the segment.
 // -----------------------------------------------------------------------------------------------------------------
-struct SolveBlkD
-{
-    const u32 *cp; // CSC
-    const u16 *ri;
-    const val_t *val;
-    u32 bcol;
-    u32 brow; // destination segment
-};
-struct SolveRowD
-{
-    u32 brow, nblk;
-    unsigned long long first; // into the SolveBlkD array
-    const u32 *dptr;          // diagonal half: lower = strictly-lower CSC column pointer, upper = CSR row pointer (diagonal first)
-    const u16 *didx;
-    const val_t *dval;
-};
-
 // x_row -= A(row, j) x_j for every off-diagonal block of the level: one workgroup per block (rows near the root of the
 // tree have hundreds of blocks: a workgroup per row would walk them one after the other), floating-point atomics on
 // the destination segment

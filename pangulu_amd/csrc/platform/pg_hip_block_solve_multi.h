@@ -1,10 +1,30 @@
 // pg_hip_block_solve_multi.h -- the device kernels of the level-scheduled block triangular solve: a PANEL of W right-hand sides per
 // launch, W = 1 for pangulu_gstrs and up to 16 for pangulu_amd_gstrs_multi (pangulu_platform_0201001_block_trsv and
 // ..._block_trsm_multi launch the same instances), and the same for the TRANSPOSED solve, A^T X = B and A^H X = B, on the records of
-// A = L U as they lie in HBM (pangulu_platform_0201001_block_trsm_multi_trans).  Included inside the anonymous namespace of
-// pg_hip_platform.hip, after pg_hip_block_solve.h (descriptors SolveBlkD / SolveRowD, the column-by-column kernels of
-// PANGULU_HIP_SOLVE_CHUNKED=0).
+// A = L U as they lie in HBM (pangulu_platform_0201001_block_trsm_multi_trans); and the descriptors SolveBlkD / SolveRowD that every
+// solve kernel reads.  Included inside the anonymous namespace of pg_hip_platform.hip, before pg_hip_block_solve.h (the
+// column-by-column kernels of PANGULU_HIP_SOLVE_CHUNKED=0) and pg_hip_launch_solve.h (the host side).
 #pragma once
+
+// One off-diagonal block and one segment (block row, or destination segment of a transposed sweep) with its diagonal half, as the
+// kernels of a level read them.  They hold device addresses of the block records.
+struct SolveBlkD
+{
+    const u32 *cp; // CSC
+    const u16 *ri;
+    const val_t *val;
+    u32 bcol;
+    u32 brow; // destination segment
+};
+struct SolveRowD
+{
+    u32 brow, nblk;
+    unsigned long long first; // into the SolveBlkD array
+    const u32 *dptr;          // diagonal half: lower = strictly-lower CSC column pointer, upper = CSR row pointer (diagonal first)
+    const u16 *didx;
+    const val_t *dval;
+};
+
 
 // -----------------------------------------------------------------------------------------------------------------
 // Round 4: two launches per level, built around where the column-by-column kernels' time went (fem27(112): 540 launches, 394 ms).

@@ -1,8 +1,8 @@
 // What the kernel emulation programs (tests/solve_multi_kernel_emulation.cpp, tests/solve_trans_kernel_emulation.cpp) put in place of
 // the device: the kernel headers of pangulu_amd/csrc/platform are compiled as plain C++ behind these shims -- a workgroup is 256
 // std::threads, __syncthreads / wave_lds_fence / __shfl_down are barriers over the workgroup / the wavefront, atomics are
-// compare-and-swap loops, the LDS is one array.  The v_* operators, ptr0 and the descriptors restate pg_hip_platform.hip and
-// pg_hip_block_solve.h; an intrinsic or operator a kernel starts to use is added HERE, once.  Include it before the kernel headers.
+// compare-and-swap loops, the LDS is one array.  The v_* operators and ptr0 restate pg_hip_platform.hip (the
+// descriptors SolveBlkD / SolveRowD are the product's own, pg_hip_block_solve_multi.h); an intrinsic or operator a kernel starts to use is added HERE, once.  Include it before the kernel headers.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -68,8 +68,6 @@ inline void v_atomic_add(val_t *d, val_t v) { if (v != 0) atomicAdd(d, v); }
 inline double vabs(val_t a) { return std::fabs(a); }
 #endif
 inline u32 ptr0(const u32 *p, int i) { return i == 0 ? 0u : p[i]; }
-struct SolveBlkD { const u32 *cp; const u16 *ri; const val_t *val; u32 bcol; u32 brow; };
-struct SolveRowD { u32 brow, nblk; unsigned long long first; const u32 *dptr; const u16 *didx; const val_t *dval; };
 
 // one launch: the workgroups one after the other, f() on each of the 256 threads of a workgroup
 template <class F> void launch(unsigned grid, F f) {
