@@ -256,6 +256,17 @@ extern "C"
      * matrix (time stepping / Newton iterations on a fixed mesh).  Collective.  Returns 0 on success, 1 when the handle was
      * built with scaling on (the matching depends on the values: call pangulu_init). */
     int pangulu_amd_update_values(void **pangulu_handle, const sparse_value_t *csc_value);
+    /* The same for values that already live where the records are (one rank): d_csc_value holds the nnz values, in the same order, in
+     * memory of the device the records are on.  Nothing but those nnz values crosses the host link (they come to the host for the
+     * factor check and the norms of pangulu_amd_rcond / pangulu_amd_factor_stats): two kernels zero the value areas of the records and
+     * put every value in its place, through a map built by the first such call and kept until pangulu_finalize.  The work is ordered
+     * behind everything queued on `stream` (a hipStream_t; NULL: the legacy default stream) at the time of the call and has completed
+     * on return.  The handle is then in the state pangulu_amd_update_values leaves it in, schedule and snapshot included, except that
+     * the host copy of the records has not been written.  On a platform whose memory is host memory the pointer is a host pointer and
+     * `stream` is ignored.  Returns 0; 1 as pangulu_amd_update_values; 2 if d_csc_value is NULL or not device memory of that device
+     * holding nnz values (asked of the runtime on the host: no kernel sees such a pointer); 4 on several ranks, where the values go
+     * through pangulu_amd_update_values.  With 1, 2 or 4 nothing has been touched. */
+    int pangulu_amd_update_values_device(void **pangulu_handle, const sparse_value_t *d_csc_value, void *stream);
     int pangulu_amd_snapshot(void **pangulu_handle);
     int pangulu_amd_reset_numeric(void **pangulu_handle);
     /* One rank: pangulu_gstrf replays the handle's recorded launch schedule (default, environment PANGULU_AMD_REPLAY) or runs

@@ -425,6 +425,34 @@ extern "C"
     int pangulu_platform_0201001_condest_vector(int step, calculate_type *d_x, calculate_type *d_save, pangulu_uint64_t n, pangulu_uint64_t j,
                                                 pangulu_condest_result_t *out, pangulu_inblock_idx nb, pangulu_uint64_t xlen,
                                                 pangulu_uint64_t n_factors, void **workspace, void *caller_stream);
+    /* Optional: new matrix values on the pattern the records were built for, written into the device-resident records from a DEVICE
+     * array (pangulu_amd_update_values_device) -- what a host does by zeroing and refilling its copy of every record and uploading all
+     * of them.  `map` says where everything goes, in offsets counted in values from the start of the arena the records live in; the
+     * arena is `nchunk` separate allocations of values_per_chunk values each (the last one may be shorter; arena_values in all):
+     *     the value areas slice_off[s] .. + slice_count[s], s < nslice, are zeroed (a slice lies within one chunk and starts on a
+     *     16-byte boundary);  then d_value[p] goes to user_dst[p], p < nuser, and const_value[c] to const_dst[c], c < nconst.
+     * The lists depend on the pattern only: they go up on the first call and stay on the device in `*device_map` (NULL before it),
+     * which the caller releases with values_refresh_free.  Two kernels on the back-end's stream, ordered behind everything queued on
+     * `caller_stream` (a hipStream_t; NULL: the legacy default stream) at the time of the call and behind whatever still writes factor
+     * records; `host_copy`, if not NULL, receives the nuser values of d_value as well.  Complete on return.
+     * Returns 1; -1 if d_value is NULL or not device memory of the back-end's device holding nuser values (decided on the host from the
+     * pointer's attributes: nothing is uploaded or launched). */
+    typedef struct pangulu_hip_values_map_t
+    {
+        pangulu_uint64_t nuser, nconst, nslice;
+        const pangulu_uint64_t *user_dst;
+        const pangulu_uint64_t *const_dst;
+        const calculate_type *const_value;
+        const pangulu_uint64_t *slice_off;
+        const pangulu_uint32_t *slice_count;
+        pangulu_uint64_t nchunk, values_per_chunk, arena_values;
+        char *const *chunks;
+    } pangulu_hip_values_map_t;
+    int pangulu_platform_0201001_values_refresh(const pangulu_hip_values_map_t *map, const calculate_type *d_value, calculate_type *host_copy,
+                                                void **device_map, void *caller_stream);
+    void pangulu_platform_0201001_values_refresh_free(void **device_map);
+    /* Device bytes held by all such maps that are alive. */
+    unsigned long long pangulu_platform_0201001_get_values_refresh_bytes(void);
     /* Optional: y[dst segment] += A_blk * x[src segment] for a list of device-resident block records, in one launch (one
      * workgroup per block, floating-point atomics on y).  `x` and `y` are HOST vectors of `xlen` values (nb per block
      * row / column); y is read, updated and written back.  csr[i] != 0: the record is an upper diagonal half (CSR, diagonal

@@ -247,6 +247,8 @@ def load(vtype="r64", test_hooks=False):
     lib.pangulu_amd_owned_block.restype = ctypes.c_int
     lib.pangulu_amd_update_values.argtypes = [vpp, vp]
     lib.pangulu_amd_update_values.restype = ctypes.c_int
+    lib.pangulu_amd_update_values_device.argtypes = [vpp, vp, vp]
+    lib.pangulu_amd_update_values_device.restype = ctypes.c_int
     lib.pangulu_amd_snapshot.argtypes = [vpp]
     lib.pangulu_amd_snapshot.restype = ctypes.c_int
     lib.pangulu_amd_reset_numeric.argtypes = [vpp]
@@ -275,6 +277,7 @@ def load(vtype="r64", test_hooks=False):
     lib.pangulu_platform_0201001_get_stats.restype = None
     lib.pangulu_platform_0201001_get_stream.restype = ctypes.c_void_p
     lib.pangulu_platform_0201001_get_solve_workspace_bytes.restype = ctypes.c_ulonglong
+    lib.pangulu_platform_0201001_get_values_refresh_bytes.restype = ctypes.c_ulonglong
     _cache[key] = lib
     return lib
 

@@ -83,6 +83,8 @@ void bind_builtin_hip(Platform &p)
     p.block_trsm_multi_trans = pangulu_platform_0201001_block_trsm_multi_trans;
     p.block_trsm_multi_device = pangulu_platform_0201001_block_trsm_multi_device;
     p.solve_workspace_free = pangulu_platform_0201001_solve_workspace_free;
+    p.values_refresh = pangulu_platform_0201001_values_refresh;
+    p.values_refresh_free = pangulu_platform_0201001_values_refresh_free;
     p.factor_stats = pangulu_platform_0201001_factor_stats;
     p.condest_vector = pangulu_platform_0201001_condest_vector;
     p.block_spmv_add = pangulu_platform_0201001_block_spmv_add;
@@ -223,6 +225,30 @@ void require_gstrs_options(const pangulu_gstrs_options *gstrs_options)
         printf("[PanguLU ERROR] Invalid input parameter. gstrs option struct pointer is NULL. Exit.\n");
     exit(1);
 }
+
+// New values on the user's pattern (pangulu_amd_update_values and pangulu_amd_update_values_device): their norms, and Aperm's values
+// rebuilt through the permutation -- the user's entry p of column j sits at (iperm[i], iperm[j]); entry order inside a permuted
+// column is by row, so each entry is located by binary search.  What no user entry maps to (padding rows' unit diagonals, inserted
+// diagonals) keeps its value.
+void new_values_into_aperm(Solver &S, const val_t *vals)
+{
+    user_matrix_norms(S.n_user, S.user_colptr.data(), S.user_rowidx.data(), vals, S.user_norm_one, S.user_norm_inf);
+    CscMatrix &B = S.Aperm;
+#pragma omp parallel for schedule(dynamic, 512)
+    for (i64 j_ = 0; j_ < (i64)S.n_user; j_++)
+    {
+        const u32 j = (u32)j_, pj = S.iperm[j];
+        for (u64 p = S.user_colptr[j]; p < S.user_colptr[j + 1]; p++)
+        {
+            const u32 pi = S.iperm[S.user_rowidx[p]];
+            const u32 *b0 = B.rowidx.data() + B.colptr[pj], *b1 = B.rowidx.data() + B.colptr[pj + 1];
+            const u32 *hit = std::lower_bound(b0, b1, pi);
+            if (hit == b1 || *hit != pi)
+                fatal("pangulu_amd_update_values: entry (%u,%u) is not in the pattern the handle was initialised with", S.user_rowidx[p], j);
+            B.value[hit - B.rowidx.data()] = vals[p];
+        }
+    }
+}
 } // namespace
 
 double pg::collective_column_solve(Solver &S, val_t *rhs, u32 nrhs, u64 ldb, int trans, bool single_vector)
@@ -319,6 +345,11 @@ extern "C"
         p.block_trsm_multi_device = (decltype(p.block_trsm_multi_device))dlsym(h, sym);
         snprintf(sym, sizeof(sym), "pangulu_platform_%07x_solve_workspace_free", platform_id);
         p.solve_workspace_free = (decltype(p.solve_workspace_free))dlsym(h, sym);
+        // ... and new values from device memory to the host loop of pg_values_refresh.cpp (a host-memory platform needs no more)
+        snprintf(sym, sizeof(sym), "pangulu_platform_%07x_values_refresh", platform_id);
+        p.values_refresh = (decltype(p.values_refresh))dlsym(h, sym);
+        snprintf(sym, sizeof(sym), "pangulu_platform_%07x_values_refresh_free", platform_id);
+        p.values_refresh_free = (decltype(p.values_refresh_free))dlsym(h, sym);
         // ... and the factor diagnostics to the host loops of pg_condest.cpp
         snprintf(sym, sizeof(sym), "pangulu_platform_%07x_factor_stats", platform_id);
         p.factor_stats = (decltype(p.factor_stats))dlsym(h, sym);
@@ -1057,27 +1088,36 @@ extern "C"
         // by row, so locate each entry by binary search
         if (S->user_colptr.size() != (size_t)S->n_user + 1)
             return 2;
-        user_matrix_norms(S->n_user, S->user_colptr.data(), S->user_rowidx.data(), vals.data(), S->user_norm_one, S->user_norm_inf);
         CscMatrix &B = S->Aperm;
-#pragma omp parallel for schedule(dynamic, 512)
-        for (i64 j_ = 0; j_ < (i64)S->n_user; j_++)
-        {
-            const u32 j = (u32)j_, pj = S->iperm[j];
-            for (u64 p = S->user_colptr[j]; p < S->user_colptr[j + 1]; p++)
-            {
-                const u32 pi = S->iperm[S->user_rowidx[p]];
-                const u32 *b0 = B.rowidx.data() + B.colptr[pj], *b1 = B.rowidx.data() + B.colptr[pj + 1];
-                const u32 *hit = std::lower_bound(b0, b1, pi);
-                if (hit == b1 || *hit != pi)
-                    fatal("pangulu_amd_update_values: entry (%u,%u) is not in the pattern the handle was initialised with", S->user_rowidx[p], j);
-                B.value[hit - B.rowidx.data()] = vals[p];
-            }
-        }
+        new_values_into_aperm(*S, vals.data());
         NearDevice near(active_platform());
         drop_solve_workspace(*S);
         reload_values(*S, B);
         if (S->arena_snapshot)
             pangulu_amd_snapshot(pangulu_handle); // (bench-style resets restore the NEW values)
+        return 0;
+    }
+
+    // The same from an array the caller already has where the records are: the back-end's kernels put the values in place
+    // (pg_values_refresh.cpp); only the nnz values themselves come to the host, for Aperm and the norms.  One rank.
+    int pangulu_amd_update_values_device(void **pangulu_handle, const sparse_value_t *d_csc_value, void *stream)
+    {
+        Solver *S = (Solver *)*pangulu_handle;
+        Platform &plat = active_platform();
+        if (!S->scale_row.empty() || S->analysis_only)
+            return 1;
+        if (S->nproc != 1 || world()->size != 1 || (!plat.host_memory && (!plat.values_refresh || !plat.values_refresh_free)))
+            return 4;
+        if (d_csc_value == nullptr || S->user_colptr.size() != (size_t)S->n_user + 1)
+            return 2;
+        NearDevice near(plat);
+        std::vector<val_t> vals(S->info.nnz);
+        if (refresh_values_from(*S, (const val_t *)d_csc_value, vals.data(), stream) != 0)
+            return 2;
+        drop_solve_workspace(*S);
+        new_values_into_aperm(*S, vals.data());
+        if (S->arena_snapshot)
+            pangulu_amd_snapshot(pangulu_handle);
         return 0;
     }
 

@@ -98,6 +98,10 @@ struct Platform
                         pangulu_factor_stats_partial_t *) = nullptr;
     int (*condest_vector)(int, val_t *, val_t *, pangulu_uint64_t, pangulu_uint64_t, pangulu_condest_result_t *, pangulu_inblock_idx, pangulu_uint64_t,
                           pangulu_uint64_t, void **, void *) = nullptr;
+    // optional: new values from device memory into the device-resident records (pangulu_amd_update_values_device), on lists the
+    // back-end keeps per handle (< 0 returned: the pointer was refused), and their release
+    int (*values_refresh)(const pangulu_hip_values_map_t *, const val_t *, val_t *, void **, void *) = nullptr;
+    void (*values_refresh_free)(void **) = nullptr;
 };
 Platform &active_platform();               // built-in HIP unless the test hook replaced it
 bool platform_is_builtin_hip();
@@ -347,6 +351,18 @@ struct SolveMaps
     bool ready = false;
 };
 
+// Where new values on the handle's pattern go (pangulu_amd_update_values_device, pg_values_refresh.cpp), as offsets into the arena
+// counted in values: the user's entry p to user_dst[p]; the entries of the permuted matrix that are not the user's (unit diagonals of
+// padding rows, inserted diagonals) with their values; and the value areas of all owned records in slices of bounded length.  A pure
+// function of the pattern and of where the records live: built on first use, fixed for the handle's life.
+struct ValuesRefreshMap
+{
+    std::vector<u64> user_dst, const_dst, slice_off;
+    std::vector<val_t> const_value;
+    std::vector<u32> slice_count;
+    bool ready = false;
+};
+
 struct Solver
 {
     // configuration
@@ -397,6 +413,8 @@ struct Solver
     // pangulu_amd_gstrs_device: what the back-end keeps on the device for this handle between calls (descriptors of the sweeps, panel
     // buffer, the maps).  It holds device addresses of records: dropped whenever the factors are about to change (drop_solve_workspace)
     void *solve_workspace = nullptr;
+    ValuesRefreshMap values_map;           // pangulu_amd_update_values_device: built by its first call
+    void *values_map_device = nullptr;     // ... and the back-end's copy of it (Platform::values_refresh), released with the handle
     // Multi-rank replay (round 4, PANGULU_AMD_MULTI_REPLAY=1): what THIS rank did in its first factorisation, in order -- the ranges
     // of the back-end's recorded operations its platform calls produced, the markers between them with the blocks that were
     // announced behind each, and which blocks of other ranks had arrived (into which receive slot) before each call was made.
@@ -495,6 +513,11 @@ double collective_column_solve(Solver &S, val_t *rhs, u32 nrhs, u64 ldb, int tra
 int triangular_solve_device(Solver &S, val_t *d_rhs, u32 nrhs, u64 ldb, int trans, void *stream, bool reproducible = false);
 bool device_solve_offered(Solver &S, int trans, bool reproducible = false); // triangular_solve_device would not return 4 for this direction (nothing touched)
 void drop_solve_workspace(Solver &S);                     // before the factors change, and when the handle goes
+// pg_values_refresh.cpp (one rank): writes the `nnz` values at `values` -- device memory behind `stream` on a device platform, host
+// memory on a host-memory one -- into the records where they are through S.values_map (built on first use), copies them to
+// `host_copy` and re-arms the handle like reload_values.  0: done; 2: the back-end refused the pointer, nothing touched
+int refresh_values_from(Solver &S, const val_t *values, val_t *host_copy, void *stream);
+void drop_values_refresh(Solver &S);                      // when the handle goes
 // pg_condest.cpp: what pangulu_amd_factor_stats and pangulu_amd_rcond do (collective)
 void user_matrix_norms(u32 n, const u64 *colptr, const u32 *rowidx, const val_t *value, double &norm_one, double &norm_inf);
 void factor_stats(Solver &S, pangulu_amd_factor_stats_t &out);

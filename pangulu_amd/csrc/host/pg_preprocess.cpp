@@ -1048,6 +1048,7 @@ Solver::~Solver()
 {
     Platform &plat = active_platform();
     drop_solve_workspace(*this);
+    drop_values_refresh(*this);
     if (schedule_recorded && plat.schedule)
         plat.schedule(0, this); // the recorded launches point into this handle's arena and mirrors
     for (char *c : snapshot_dchunks)

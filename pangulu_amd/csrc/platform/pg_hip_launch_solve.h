@@ -404,6 +404,94 @@ bool solve_pointer_on_device(const void *p, size_t bytes)
     return (const char *)p >= (const char *)base && (const char *)p + bytes <= (const char *)base + size;
 }
 
+// What pangulu_platform_0201001_values_refresh keeps on the device for a handle: the lists of pangulu_hip_values_map_t and the table of
+// the arena's chunks.  They depend on the pattern and on where the records live, so they stay until the host releases them.
+struct ValuesRefreshMapD
+{
+    unsigned long long *d_user_dst = nullptr, *d_const_dst = nullptr, *d_slice_off = nullptr;
+    val_t *d_const_value = nullptr;
+    u32 *d_slice_count = nullptr;
+    val_t **d_chunks = nullptr;
+    size_t nuser = 0, nconst = 0, nslice = 0, vpc = 0;
+    int chunk_shift = -1; // vpc == 1 << chunk_shift, or -1
+    unsigned ncu = 1;
+    hipEvent_t after_caller = nullptr;
+    size_t bytes = 0;
+};
+size_t g_values_refresh_bytes = 0; // (under B.mutex)
+
+void values_refresh_map_release(ValuesRefreshMapD *D) // B.mutex held
+{
+    HIP_CHECK(hipSetDevice(B.device));
+    HIP_CHECK(hipStreamSynchronize(B.stream));
+    for (void *p : {(void *)D->d_user_dst, (void *)D->d_const_dst, (void *)D->d_slice_off, (void *)D->d_const_value, (void *)D->d_slice_count, (void *)D->d_chunks})
+        if (p)
+            HIP_CHECK(hipFree(p));
+    if (D->after_caller)
+        HIP_CHECK(hipEventDestroy(D->after_caller));
+    g_values_refresh_bytes -= D->bytes;
+    delete D;
+}
+
+// the handle's lists on the device, checked and uploaded when they are not there (B.mutex held).  Every place the kernels will write
+// is checked against the arena here, on the host, once: no kernel sees a list that fails.
+ValuesRefreshMapD *values_refresh_map_of(void **device_map, const pangulu_hip_values_map_t &M)
+{
+    if (*device_map)
+        return (ValuesRefreshMapD *)*device_map;
+    const unsigned long long vpc = M.values_per_chunk;
+    bool ok = vpc > 0 && M.nchunk > 0 && M.chunks && M.arena_values <= M.nchunk * vpc && M.arena_values > (M.nchunk - 1) * vpc;
+    for (unsigned long long c = 0; ok && c < M.nchunk; c++)
+        ok = M.chunks[c] != nullptr;
+    for (unsigned long long k = 0; ok && k < M.nuser; k++)
+        ok = M.user_dst[k] < M.arena_values;
+    for (unsigned long long k = 0; ok && k < M.nconst; k++)
+        ok = M.const_dst[k] < M.arena_values;
+    for (unsigned long long s = 0; ok && s < M.nslice; s++)
+    {
+        const unsigned long long o = M.slice_off[s], n = M.slice_count[s];
+        ok = n > 0 && o < M.arena_values && n <= M.arena_values - o && o / vpc == (o + n - 1) / vpc && (o % vpc) * sizeof(val_t) % 16 == 0;
+    }
+    if (!ok)
+    {
+        fprintf(stderr, "[PanguLU-AMD ERROR] values_refresh: a destination outside the arena of %llu values in %llu chunks of %llu\n",
+                (unsigned long long)M.arena_values, (unsigned long long)M.nchunk, vpc);
+        exit(EXIT_FAILURE);
+    }
+    ValuesRefreshMapD *D = new ValuesRefreshMapD();
+    D->nuser = (size_t)M.nuser;
+    D->nconst = (size_t)M.nconst;
+    D->nslice = (size_t)M.nslice;
+    D->vpc = (size_t)vpc;
+    if ((vpc & (vpc - 1)) == 0)
+        for (D->chunk_shift = 0; (1ull << D->chunk_shift) != vpc; D->chunk_shift++)
+        {
+        }
+    int ncu = 0;
+    HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, B.device));
+    D->ncu = (unsigned)std::max(ncu, 1);
+    // (an empty list still gets an allocation: the kernels take the pointer and read nothing)
+    auto up = [&](auto **p, const auto *src, size_t count)
+    {
+        const size_t bytes = sizeof(**p) * std::max<size_t>(count, 1);
+        HIP_CHECK(hipMalloc((void **)p, bytes));
+        D->bytes += bytes;
+        g_values_refresh_bytes += bytes;
+        if (count)
+            HIP_CHECK(hipMemcpyAsync(*p, src, sizeof(**p) * count, hipMemcpyHostToDevice, B.stream));
+    };
+    up(&D->d_user_dst, M.user_dst, D->nuser);
+    up(&D->d_const_dst, M.const_dst, D->nconst);
+    up(&D->d_const_value, (const val_t *)M.const_value, D->nconst);
+    up(&D->d_slice_off, M.slice_off, D->nslice);
+    up(&D->d_slice_count, M.slice_count, D->nslice);
+    up(&D->d_chunks, (val_t *const *)M.chunks, (size_t)M.nchunk);
+    HIP_CHECK(hipStreamSynchronize(B.stream)); // (the caller's lists may go once this returns)
+    HIP_CHECK(hipEventCreateWithFlags(&D->after_caller, hipEventDisableTiming));
+    *device_map = D;
+    return D;
+}
+
 // pack (into = true) or unpack a panel of w right-hand sides
 void launch_solve_pack_of(int w, bool into, val_t *d_rhs, size_t ldb, u32 j0, u32 nc, const SolveWorkspace &ws, const SolveWorkspace::Direction &D)
 {

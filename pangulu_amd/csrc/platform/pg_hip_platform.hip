@@ -808,6 +808,7 @@ namespace
 #include "pg_hip_block_solve.h"
 #include "pg_hip_solve_pack.h"
 #include "pg_hip_factor_stats.h"
+#include "pg_hip_values_refresh.h"
 
 #include "pg_hip_backend.h"
 
@@ -1661,6 +1662,54 @@ extern "C"
     {
         std::lock_guard<std::mutex> g(B.mutex);
         return (unsigned long long)g_solve_workspace_bytes;
+    }
+
+    // New values into the device-resident records (pg_hip_values_refresh.h): the lists go up once per handle; per call the two kernels
+    // on B.stream behind the caller's stream and behind whatever still writes records, one synchronisation at the end.
+    int pangulu_platform_0201001_values_refresh(const pangulu_hip_values_map_t *map, const calculate_type *d_value, calculate_type *host_copy,
+                                                void **device_map, void *caller_stream)
+    {
+        if (!map || !device_map)
+        {
+            fprintf(stderr, "[PanguLU-AMD ERROR] values_refresh: no map\n");
+            exit(EXIT_FAILURE);
+        }
+        ensure_ready();
+        std::lock_guard<std::mutex> g(B.mutex);
+        HIP_CHECK(hipSetDevice(B.device));
+        if (!d_value || !solve_pointer_on_device(d_value, sizeof(val_t) * (size_t)map->nuser))
+            return -1;
+        // (sparsify jobs of the previous factorisation write the very value areas the first kernel clears)
+        solve_join_factor_streams();
+        ValuesRefreshMapD *D = values_refresh_map_of(device_map, *map);
+        HIP_CHECK(hipEventRecord(D->after_caller, (hipStream_t)caller_stream));
+        HIP_CHECK(hipStreamWaitEvent(B.stream, D->after_caller, 0));
+        hipLaunchKernelGGL(values_clear_kernel, dim3(values_refresh_grid(D->nslice, 1, 4 * D->ncu)), dim3(256), 0, B.stream, D->d_slice_off,
+                           D->d_slice_count, (unsigned long long)D->nslice, D->d_chunks, (unsigned long long)D->vpc, D->chunk_shift);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(values_scatter_kernel, dim3(values_refresh_grid(std::max(D->nuser, D->nconst), 256, 8 * D->ncu)), dim3(256), 0, B.stream,
+                           (const val_t *)d_value, D->d_user_dst, (unsigned long long)D->nuser, D->d_const_value, D->d_const_dst,
+                           (unsigned long long)D->nconst, D->d_chunks, (unsigned long long)D->vpc, D->chunk_shift);
+        HIP_CHECK(hipGetLastError());
+        if (host_copy && D->nuser)
+            HIP_CHECK(hipMemcpyAsync(host_copy, d_value, sizeof(val_t) * D->nuser, hipMemcpyDeviceToHost, B.stream));
+        HIP_CHECK(hipStreamSynchronize(B.stream));
+        return 1;
+    }
+
+    void pangulu_platform_0201001_values_refresh_free(void **device_map)
+    {
+        if (!device_map || !*device_map)
+            return;
+        std::lock_guard<std::mutex> g(B.mutex);
+        values_refresh_map_release((ValuesRefreshMapD *)*device_map);
+        *device_map = nullptr;
+    }
+
+    unsigned long long pangulu_platform_0201001_get_values_refresh_bytes(void)
+    {
+        std::lock_guard<std::mutex> g(B.mutex);
+        return (unsigned long long)g_values_refresh_bytes;
     }
 
     // One launch over the listed records (pg_hip_factor_stats.h): descriptors and the padding mask up, one partial per record back.

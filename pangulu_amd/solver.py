@@ -290,10 +290,41 @@ def factors_as_scipy(h):
     return L.tocsc(), U.tocsc()
 
 
+def _update_values_torch(torch, h, T):
+    """update_values for a torch tensor of nnz values.  Where pangulu_amd_update_values_device has no path for the handle (return
+    code 4: several ranks) the values are staged through the host."""
+    want = getattr(torch, np.dtype(h.dtype).name)
+    if T.dtype != want:
+        raise TypeError("the handle holds %s values, the tensor holds %s" % (want, T.dtype))
+    nnz = int(h.info()["nnz"])
+    if T.ndim != 1 or T.shape[0] != nnz:
+        raise ValueError("a tensor of shape (%d,) is expected, got %r" % (nnz, tuple(T.shape)))
+    V = T.detach()
+    if not V.is_cuda:
+        return update_values(h, V.numpy())
+    V = V.contiguous()
+    with torch.cuda.device(V.device):
+        stream = torch.cuda.current_stream().cuda_stream
+    rc = h.lib.pangulu_amd_update_values_device(h.ref, ctypes.c_void_p(V.data_ptr()), ctypes.c_void_p(stream))
+    if rc == 2:
+        raise ValueError("the tensor is on %s, not on the device the records are on" % (V.device,))
+    if rc == 4:
+        return update_values(h, V.cpu().numpy())
+    if rc != 0:
+        raise RuntimeError("pangulu_amd_update_values_device failed (%d)" % rc)
+
+
 def update_values(h, csc_value):
     """New values on the pattern the handle was initialised with (same order as the csc_rowidx given to pangulu_init; rank 0):
     the next pangulu_gstrf factorises the new matrix, re-using ordering, symbolic factorisation, records and -- on one rank --
-    the recorded launch schedule."""
+    the recorded launch schedule.
+
+    csc_value may be a torch tensor of the handle's dtype holding the nnz values (one rank).  A tensor on the device the records are
+    on is taken from there, behind torch's current stream, by pangulu_amd_update_values_device: only the nnz values cross the host
+    link, not the records.  A CPU tensor takes the numpy path."""
+    torch = _torch_if_tensor(csc_value)
+    if torch is not None:
+        return _update_values_torch(torch, h, csc_value)
     if csc_value is not None:
         va = np.ascontiguousarray(csc_value, dtype=h.dtype)  # (alive until the call returns: the library copies the values)
         ptr = va.ctypes.data_as(ctypes.c_void_p)
@@ -383,12 +414,13 @@ def model_for_ranks(h, nranks):
 
 def hip_memory(h_or_lib):
     """Device memory the back-end holds for itself (bytes): mirror pool, descriptor twins of a recorded schedule, GETRF scratch,
-    the workspaces of device-resident solves; and the number of blocks in dense mode."""
+    the workspaces of device-resident solves, the maps of update_values from device memory; and the number of blocks in dense mode."""
     lib = h_or_lib.lib if isinstance(h_or_lib, Handle) else h_or_lib
     v = (ctypes.c_ulonglong * 4)()
     lib.pangulu_platform_0201001_get_memory(v)
     return {"mirror_pool_bytes": int(v[0]), "schedule_descriptor_bytes": int(v[1]), "getrf_scratch_bytes": int(v[2]), "dense_mode_blocks": int(v[3]),
-            "solve_workspace_bytes": int(lib.pangulu_platform_0201001_get_solve_workspace_bytes())}
+            "solve_workspace_bytes": int(lib.pangulu_platform_0201001_get_solve_workspace_bytes()),
+            "values_refresh_bytes": int(lib.pangulu_platform_0201001_get_values_refresh_bytes())}
 
 
 def hip_stats(h_or_lib, reset=False):

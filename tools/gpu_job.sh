@@ -12,6 +12,7 @@
 #   repeat <n> <pytest node id>      the same test n times, stop at the first failure (start-up races) -> gpurun_out/<TAG>_repeat.log
 #   launchlog [bench.py flags]       per-launch log of the profiled factorisation + tools/launch_log_summary.py
 #   solve [bench_solve.py flags]     tools/bench_solve.py: block solves beside single pangulu_gstrs calls -> its JSON line on stdout
+#   values [bench_update_values.py flags]  tools/bench_update_values.py: new values from a numpy array beside a CUDA tensor -> its JSON line on stdout
 #
 # TAG (environment, default "job") names the outputs.  Everything is written under gpurun_out/ (scratch; copy what is to be judged
 # into profiles/ and add its line to profiles/INDEX.md).
@@ -89,6 +90,10 @@ repeat)
 solve)
     timeout -k 10 ${SOLVE_TIMEOUT:-500} python3 tools/bench_solve.py "$@"
     echo "[gpu_job solve] rc=$?"
+    ;;
+values)
+    timeout -k 10 ${VALUES_TIMEOUT:-500} python3 tools/bench_update_values.py "$@"
+    echo "[gpu_job values] rc=$?"
     ;;
 launchlog)
     set -- --full "$@"  # (the log is of the profile pass, which a plain bench.py run does not make)
