@@ -91,6 +91,13 @@ struct Backend
     // selected round 3's ssssm_tiles_f64_kernel<STAGES> and round 5's ssssm_tilesp_f64_kernel: tools/experiments/ since round 6.)
     long long opt_tiles_stages = 2; // PANGULU_HIP_TILES_STAGES / option 16
     long long opt_tiles_unit = 1;   // PANGULU_HIP_TILES_UNIT: consecutive destinations of the general launch that share an XCD
+    // Longest queues first (PANGULU_HIP_HEAVY_FIRST): a launch ends with its last workgroup, and a queue of 128 live slab
+    // steps that starts when the others are done is a tail of its own length.  Classes by the live steps of a group's
+    // busiest tile -- sixteen of 16 steps each (2, the default), or four (1) --, the scheduler's order kept inside a class
+    // (neighbours share operands: L2); 0 = the scheduler's order (plan_update_work, pg_hip_update_plan.h).  fem27(112), one
+    // box: 810.3-811.6 / 813.3 / 815.4 ms with 2 / 1 / 0 (profiles/r03ak_heavy_first.log); shell(398) indifferent.
+    long long opt_heavy_first = 2;
+    bool opt_debug_ssssm = false; // PANGULU_HIP_DEBUG_SSSSM (set to anything): phase stamps of ssssm_dense_f64_kernel (they share the GETRF debug slots)
     unsigned long long front_workgroups = 0, general_workgroups = 0;
     long long opt_records_stream = 1; // PANGULU_HIP_RECORDS_STREAM=0: sparsify on the main stream as before
     int nb_cfg = 0;
@@ -345,6 +352,9 @@ void ensure_ready()
         B.opt_group_chunk = atol(e);
     if (const char *e = getenv("PANGULU_HIP_TILES_UNIT"))
         B.opt_tiles_unit = atol(e);
+    if (const char *e = getenv("PANGULU_HIP_HEAVY_FIRST"))
+        B.opt_heavy_first = atoi(e);
+    B.opt_debug_ssssm = getenv("PANGULU_HIP_DEBUG_SSSSM") != nullptr;
     if (const char *e = getenv("PANGULU_HIP_DENSE_PERMILLE"))
         B.opt_dense_permille = atol(e);
     if (const char *e = getenv("PANGULU_HIP_TRSM_DENSE_PERMILLE"))

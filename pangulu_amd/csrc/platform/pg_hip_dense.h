@@ -57,8 +57,7 @@ __device__ inline const unsigned short *mirror_map(const double *mirror, int nb)
 // the two steps past the end of the list, load 16 bytes from the start of the mirror instead (an L1 hit, never used) --
 // which keeps the count between "loads of step j+1" and "now" a compile-time constant (8).
 // ---------------------------------------------------------------------------------------------------------------
-#define DG_TILE 128
-#define DG_K 16
+#define DG_K 16 // (DG_TILE, the tile edge: pg_hip_update_desc.h)
 // a workgroup-uniform address pinned in scalar registers: the compiler otherwise folds it into 64-bit per-lane arithmetic
 // (base + lane offset first, then the uniform part on top, in vector instructions) instead of the scalar-base form of
 // global_load / global_store (scalar base + 32-bit lane offset + immediate)

@@ -2,8 +2,6 @@
 // pg_hip_platform.hip, after Backend / Segment / host_nnz / diag_halves).
 #pragma once
 
-#if defined(PG_DENSE_UPDATES)
-
 struct BlockState
 {
     double *mirror = nullptr;
@@ -514,11 +512,3 @@ void reset_block_states()
     MP.to_sparsify.clear();
     MP.early.clear();
 }
-
-#else // other value types have no dense mode
-
-inline bool dense_mode_available(int) { return false; }
-inline void require_sparse(slot_t *, int) {}
-inline void reset_block_states() {}
-
-#endif

@@ -148,13 +148,11 @@ void launch_getrf(int nb, task_t **list, size_t n, hipStream_t gs, bool defer_jo
             by += (2 * SV + 2) * ((double)host_nnz(lo, nb) + host_nnz(up, nb)) + 8.0 * (nb + 1);
         }
         hipStream_t ks = gs;
-#if defined(PG_DENSE_UPDATES)
         if (!MP.to_sparsify.empty())
         {
             flush_mirror_jobs(nb, MP.to_sparsify, false); // (main stream) these blocks must see it: stay on the main stream
             ks = B.stream;
         }
-#endif
 #if defined(PG_COMPLEX_PANELS)
         ZGetrfTaskD *d_ztasks = nullptr;
         GetrfTaskD *d_zcount = nullptr;

@@ -36,7 +36,6 @@
 #include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
-#include <unordered_set>
 #include <vector>
 
 #include "../../../include/pangulu_platform.h"
@@ -140,7 +139,6 @@ __device__ inline val_t clamp_pivot(val_t p)
 // and every dense kernel is the f64 one: the arithmetic between two rounding points is at least the reference's (cuBLAS
 // sgemm / cgemm on densified blocks, ...0201000.cu:778-816), one code path serves all four types, and the f64 matrix
 // cores of gfx950 run at half the f32 rate, not at a fraction of it.
-#define PG_DENSE_UPDATES 1
 #if defined(CALCULATE_TYPE_R64) || defined(CALCULATE_TYPE_R32)
 #define PG_DENSE_PANELS 1
 #endif
@@ -154,63 +152,7 @@ __device__ inline val_t clamp_pivot(val_t p)
 // -----------------------------------------------------------------------------------------------------------------
 // device-side descriptors
 // -----------------------------------------------------------------------------------------------------------------
-struct BlkView // one compressed view of a block: pointer array over the major dimension, minor indices, values
-{
-    const u32 *ptr;
-    const u16 *idx;
-    val_t *val;
-};
-
-struct SsssmTaskD
-{
-    BlkView a; // op1 (L block), CSC
-    BlkView b; // op2 (U block), CSC
-    // MFMA kernel only.  CR64: a complex update is four real products on the planes of the mirrors; `sign` multiplies the A
-    // operand (the A_im B_im product ADDS to the real plane), `count` marks the one of the four whose structural flops count
-    double sign;
-    u32 count;
-    // has_map: amap / bmap_t hold the occupancy of the operands (from the host's summaries, BlockState::occ_map):
-    //   amap[s]   bit r: A has pattern entries in row slab r of K-slab (column slab) s
-    //   bmap_t[s] bit c: B has pattern entries in column slab c of K-slab (row slab) s
-    // otherwise (blocks received from another rank) the kernel reads the maps behind the mirrors
-    u32 has_map;
-    unsigned short amap[16], bmap_t[16];
-};
-static_assert(sizeof(SsssmTaskD) == 128, "two task descriptors per 256 bytes");
-
-// one workgroup of the MFMA update launch: a 128 x 128 tile of one destination and the queue of updates that reach it
-struct SsssmWorkD
-{
-    val_t *cdense;          // the destination's mirror (CR64: one plane of it)
-    u32 task_begin, task_end;
-    u32 atomic, slab_mask;  // as in SsssmGroupD
-    u32 tile, pad_;
-};
-
-struct SsssmGroupD
-{
-    BlkView c;        // destination CSC (diagonal destination: its strictly-lower half)
-    // diagonal destination only: column view of the upper half (built once per diagonal block, see DiagAux)
-    const u32 *ucp;
-    const u16 *uri;
-    const u32 *uvi;
-    val_t *uval;
-    // dense-mode destination: its nb x nb column-major mirror (see pg_hip_dense.h); the sparse views above are unused
-    val_t *cdense;
-    u32 task_begin, task_end;
-    // a destination with many queued updates is cut into several groups that run concurrently: each then starts
-    // from zero and ADDS its partial sum to the destination with floating-point atomics (otherwise the longest
-    // queue sets the duration of the whole launch)
-    u32 atomic;
-    // MFMA kernel, nb <= 256: bit s set = this group works on K-slab s (16 wide) of every task; 0 = all slabs.  A launch
-    // with a handful of updates (the diagonal block's update near the root of the tree, on the critical path of
-    // every level) is cut four ways along K so that 16 CUs instead of 4 share a 256 x 256 x 256 product.
-    u32 slab_mask;
-    // host side only: which of the destination's 128 x 128 tiles some update of this group can reach (bit = tile index);
-    // the launch leaves the others out (pangulu_platform_0201001_prepare_blocks)
-    u32 live_tiles;
-    u32 pad_;
-};
+#include "pg_hip_update_desc.h" // BlkView, SsssmTaskD, SsssmWorkD, SsssmGroupD
 
 struct TrsmTaskD
 {
@@ -516,11 +458,9 @@ __global__ __launch_bounds__(SSSSM_WAVES * 64) void ssssm_sparse_kernel(const Ss
 // -----------------------------------------------------------------------------------------------------------------
 // SSSSM, dense (R64) and the dense-mode mirrors: pg_hip_dense.h
 // -----------------------------------------------------------------------------------------------------------------
-#if defined(PG_DENSE_UPDATES)
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 #include "pg_hip_dense.h"
 #include "pg_hip_front.h"
-#endif
 #if defined(PG_DENSE_PANELS) || defined(PG_COMPLEX_PANELS)
 #include "pg_hip_trsm_dense.h"
 #include "pg_hip_trsm_ring.h"
@@ -801,6 +741,8 @@ __global__ void getrf_flop_count_kernel(const GetrfTaskD *__restrict__ tasks, in
 // =================================================================================================================
 // host side of the back-end
 // =================================================================================================================
+#include "pg_hip_update_plan.h" // (standard headers of its own: outside the namespace)
+
 namespace
 {
 
@@ -825,9 +767,7 @@ void prefetch_task_details(const task_t *t, int nb)
         {
             if (s->columnpointer)
                 __builtin_prefetch(&s->columnpointer[nb]);
-#if defined(PG_DENSE_UPDATES)
             MP.blocks.prefetch(block_key(s));
-#endif
         }
 }
 constexpr size_t PREFETCH_SLOTS_AHEAD = 24, PREFETCH_DETAILS_AHEAD = 12;
@@ -1362,7 +1302,6 @@ extern "C"
     void pangulu_platform_0201001_prepare_blocks(pangulu_inblock_idx nb, pangulu_uint64_t nslot, pangulu_storage_slot_t **slots)
     {
         flush_pending_getrf_locked();
-#if defined(PG_DENSE_UPDATES)
         if (nb > 256 || nb % 16 != 0 || nslot == 0)
             return;
         static const bool enabled = !(getenv("PANGULU_HIP_OCCUPANCY_SUMMARIES") && atoi(getenv("PANGULU_HIP_OCCUPANCY_SUMMARIES")) == 0);
@@ -1429,11 +1368,6 @@ extern "C"
             memcpy(st.occ_map, occ[i].map, sizeof(st.occ_map));
             memcpy(st.occ_map_t, occ[i].map_t, sizeof(st.occ_map_t));
         }
-#else
-        (void)nb;
-        (void)nslot;
-        (void)slots;
-#endif
     }
 
     int pangulu_platform_0201001_set_option(int option, long long value)
@@ -1884,11 +1818,9 @@ extern "C"
         }
         for (hipEvent_t e : REC.early_events)
             (void)hipEventDestroy(e);
-#if defined(PG_DENSE_UPDATES)
         MP.early.clear();
         MP.early_h = MP.early_d = nullptr; // (the segment went with the recording)
         MP.early_cap = MP.early_used = 0;
-#endif
         REC = Recorder();
     }
 
@@ -1996,7 +1928,6 @@ extern "C"
                 B.chase_launches = REC.wgs_before[2];
                 B.chase_solves = REC.wgs_before[3];
             }
-#if defined(PG_DENSE_UPDATES)
             if (!MP.early.empty())
             {
                 // (every launch function flushes what it moved: this cannot happen)
@@ -2007,7 +1938,6 @@ extern "C"
                 fprintf(stderr, "[pangulu_amd trace] schedule: %llu first-touch densify jobs moved into %llu prologue chunks on the early stream\n",
                         MP.early_jobs, MP.early_chunks);
             MP.early_jobs = MP.early_chunks = 0;
-#endif
             REC.nb = B.nb_cfg;
             REC.generation = B.generation; // (the allocations of the recording itself are behind us)
             REC.valid = true;
@@ -2095,10 +2025,8 @@ extern "C"
     {
         std::lock_guard<std::mutex> g(B.mutex);
         out[0] = out[1] = out[2] = out[3] = 0;
-#if defined(PG_DENSE_UPDATES)
         out[0] = (unsigned long long)MP.chunks.size() * MP.chunk_bytes;
         out[3] = (unsigned long long)MP.peak;
-#endif
         out[1] = (unsigned long long)REC.descriptor_bytes;
         out[2] = B.getrf_scratch ? (unsigned long long)B.getrf_scratch_slots * std::max(sizeof(val_t), sizeof(double)) * (size_t)B.nb_cfg * B.nb_cfg : 0ull;
     }
@@ -2121,7 +2049,7 @@ extern "C"
         harvest_events();
         unsigned long long f[PG_FLOP_WORDS];
         HIP_CHECK(hipMemcpy(f, B.d_flops, sizeof(f), hipMemcpyDeviceToHost));
-        if (getenv("PANGULU_HIP_DEBUG_SSSSM"))
+        if (B.opt_debug_ssssm)
             fprintf(stderr, "[ssssm_dense stamps, every 64th workgroup, shader clocks] bookkeeping+first step %llu | barrier A %llu | LDS stage (waits for the slab) %llu | barrier B %llu | next step + loads issued %llu | mfma %llu | C update %llu | slab steps %llu, empty workgroups %llu\n",
                     f[8], f[9], f[10], f[11], f[12], f[13], f[14], f[15] & 0xFFFFFFFFull, f[15] >> 32);
         if (getenv("PANGULU_HIP_DEBUG_TRSM"))

@@ -7,9 +7,7 @@
 typedef double val_t;
 typedef unsigned int u32;
 typedef unsigned short u16;
-struct BlkView { const u32 *ptr; const u16 *idx; val_t *val; };
-struct SsssmTaskD { BlkView a, b; };
-struct SsssmGroupD { BlkView c; const u32 *ucp; const u16 *uri; const u32 *uvi; val_t *uval; val_t *cdense; u32 task_begin, task_end; u32 atomic; u32 slab_mask; u32 live_tiles; u32 pad_; }; // = pg_hip_platform.hip
+#include "../../pangulu_amd/csrc/platform/pg_hip_update_desc.h"
 __device__ inline u32 ptr0(const u32 *p, int i) { return i == 0 ? 0u : p[i]; }
 __device__ inline unsigned long long wave_sum(unsigned long long v) { for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64); return v; }
 typedef double v4f64 __attribute__((ext_vector_type(4)));

@@ -14,9 +14,7 @@ typedef unsigned short u16;
 #define PG_PLANES 1
 #define PG_DENSE_PANELS 1
 #define PANGULU_TOL 1e-16
-struct BlkView { const u32 *ptr; const u16 *idx; val_t *val; };
-struct SsssmTaskD { BlkView a, b; double sign; u32 count; u32 has_map; unsigned short amap[16], bmap_t[16]; };
-struct SsssmWorkD { val_t *cdense; u32 task_begin, task_end; u32 atomic, slab_mask; u32 tile, pad_; };
+#include "../../pangulu_amd/csrc/platform/pg_hip_update_desc.h"
 struct GetrfTaskD { const u32 *lcp; const u16 *lri; val_t *lval; const u32 *urp; const u16 *uci; val_t *uval; val_t *dense; u32 preloaded, invert_tiles, defer_gather; };
 __device__ inline u32 ptr0(const u32 *p, int i) { return i == 0 ? 0u : p[i]; }
 __device__ inline unsigned long long wave_sum(unsigned long long v) { for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64); return v; }

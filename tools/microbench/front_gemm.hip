@@ -14,10 +14,7 @@ typedef double val_t;
 typedef unsigned int u32;
 typedef unsigned short u16;
 #define PG_PLANES 1
-struct BlkView { const u32 *ptr; const u16 *idx; val_t *val; };
-struct SsssmTaskD { BlkView a, b; double sign; u32 count; u32 has_map; unsigned short amap[16], bmap_t[16]; }; // = pg_hip_platform.hip
-static_assert(sizeof(SsssmTaskD) == 128, "descriptor layout");
-struct SsssmWorkD { val_t *cdense; u32 task_begin, task_end; u32 atomic, slab_mask; u32 tile, pad_; };
+#include "../../pangulu_amd/csrc/platform/pg_hip_update_desc.h"
 __device__ inline u32 ptr0(const u32 *p, int i) { return i == 0 ? 0u : p[i]; }
 __device__ inline unsigned long long wave_sum(unsigned long long v) { for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64); return v; }
 typedef double v4f64 __attribute__((ext_vector_type(4)));
